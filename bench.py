@@ -2,6 +2,16 @@
 """bench.py — rollouts/s of the MPPI control step on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--workload pm3d|pm2d|pm1d|mlp|mlp32|auv|nnauv|nnspeed] [--horizon H] [--samples K_PER_GPU] [--bf16x3 | --fp-contract]
+                    [--dump-outputs DIR] [--full]
+
+A plain run is the headline alone: set up, warm up (SETTLE_S seconds of steps, undone, then W warm-up steps), EXACTLY K timed
+steps (one batch), the outputs if --dump-outputs is given, the JSON line. `--full` adds everything else this file measures: the
+kernel-duration pass and the roofline, the sub-records of the other configurations, the host-synchronous and pre-launched figures,
+the CPU baseline, and (N > 1) the sharded parity verdict.
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the step receives it: DIR/u.npy (the control),
+DIR/action_sequence.npy (the updated nominal sequence U) and DIR/costs.npy (the K rollout costs of rank 0's shard), fp32; with
+N > 1, rank 0 of the first job that produced a line writes them.
+The inputs are fixed by the arguments (seeded Philox noise, x0, U = 0, synthetic or seeded weights), so two builds compare output for output.
 
 `--gpus N` with N > 1 works as typed: the parent process — before anything touches a GPU — starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...` as a CHILD
@@ -12,21 +22,22 @@ A "step" is ONE control step of the hot path: K rollouts x H model steps + costs
 state x and the nominal sequence U already resident in HBM and the noise drawn on the device (Philox).
 Headline workload at N=1: BASELINE configs[2], point_mass3d analytic, K=65536, H=64 — the configuration the metric is
 quoted on. Every BASELINE config is launchable:
-    configs[1]  --workload pm2d --samples 4096                 (also a sub-record of the default run; its step is ONE launch, k_step_pc)
+    configs[1]  --workload pm2d --samples 4096                 (also a sub-record of the default --full run; its step is ONE launch, k_step_pc)
     configs[2]  (default)
-    configs[3]  --workload mlp                                 (also a sub-record of the default run, with the split-bf16 variant)
-    configs[4]  --workload mlp --horizon 128 --gpus 8          (K = 65536 per rank = 524288 in all; a sub-record of every N>1 run)
+    configs[3]  --workload mlp                                 (also a sub-record of the default --full run, with the split-bf16 variant)
+    configs[4]  --workload mlp --horizon 128 --gpus 8          (K = 65536 per rank = 524288 in all; a sub-record of every N>1 --full run)
     (mlp32 / nnauv / auv: the reference's own Dense(32)x3 network, its NNAUVModel shape (s=13, a=6) and its Fossen AUVModel —
-     not BASELINE configs; sub-records of the default run)
+     not BASELINE configs; sub-records of the default --full run)
 N>1 is WEAK scaling: every rank keeps --samples rollouts of a (samples x N)-sample controller, one exchange of the
 (beta, eta, V) record per step. Rank 0 prints ONE JSON line (value = whole-job rollouts/s, max-over-ranks time).
 
-Timing: W warm-up steps, then batches of EXACTLY K steps, each bracketed by barrier + synchronize on both sides and
-reduced with MAX over ranks; batches repeat until --min-time seconds have been TIMED (default 1 s, whatever K is: a 200-step
-batch of the analytic workload is 4 ms, one batch is a noisy sample), `value` is the MEDIAN batch; the kernel durations come
-from >= 200 launches bracketed by the dispatches' own timestamps. `ms_per_control_step_sync` is the host-synchronous
+Timing: SETTLE_S seconds of steps (the clocks' ramp; the controller's state is then put back), W warm-up steps, then one batch
+of EXACTLY K steps, bracketed by barrier + synchronize on both sides and reduced with MAX over ranks; with --min-time T, batches
+of K steps repeat until T seconds have been TIMED (a 200-step batch of the analytic workload is 4 ms, one batch is a noisy sample)
+and `value` is the MEDIAN batch. With --full, the kernel durations come
+from >= 200 launches bracketed by the dispatches' own timestamps. `ms_per_control_step_sync` (--full) is the host-synchronous
 mppi_next figure, with armed launches (MPPI_TUNE_ARMED_US) where the handle supports them and launch-per-call beside it.
-N > 1 lines carry `parity` (sharded_parity below). The line stays below 4 KB: what each field means is written in DESIGN.md §6.
+N > 1 --full lines carry `parity` (sharded_parity below). The line stays below 4 KB: what each field means is written in DESIGN.md §6.
 """
 import argparse
 import json
@@ -41,6 +52,7 @@ sys.path.insert(0, ROOT)
 T_START = time.time()
 
 HID = 256                                 # BASELINE configs[3]: learned 2x256 MLP model_base
+SETTLE_S = 0.5                            # seconds the headline step runs before its warm-up (Runner.run): the clocks' ramp
 HBM_PEAK_GBS = 8000.0                     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3              # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, exact fp32
 MFMA_BF16_PEAK_TFLOPS = 2500.0
@@ -57,22 +69,41 @@ CONFIG_NAME = {("pm1d", 128, 32, 1): "configs[0]", ("pm2d", 4096, 64, 1): "confi
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="K steps per timed batch (default 200; 20 for the MLP workload, ~5 ms per step)")
+    ap.add_argument("--steps", type=int, default=None, help="K timed steps, one batch (default 200; 20 for the MLP workload, ~5 ms per step)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None,
-                    help="default: pm3d (BASELINE configs[2], the metric's config) plus sub-records of the other configs")
+                    help="default: pm3d (BASELINE configs[2], the metric's config); with --full plus sub-records of the other configs")
     ap.add_argument("--horizon", type=int, default=None, help="H (default 64; 32 for pm1d)")
     ap.add_argument("--samples", type=int, default=None, help="rollouts PER GPU (default 65536; 4096 for pm2d, 128 for pm1d)")
-    ap.add_argument("--min-time", type=float, default=1.0, help="repeat the K-step batch until this many seconds are timed (headline only)")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="repeat the K-step batch until this many seconds are timed (headline only; default: one batch, exactly K timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel-duration pass and roofline, the sub-records, the synchronous / pre-launched figures, the CPU baseline and "
+                         "(N > 1) the parity verdict; a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's u, action sequence and rollout costs as DIR/<name>.npy (fp32)")
     ap.add_argument("--bf16x3", action="store_true", help="the split-bf16 matrix-core variant of a learned-model workload (MPPI_FLAG_MLP_BF16X3)")
     ap.add_argument("--fp-contract", action="store_true", help="the contracted instance of the point-mass rollout (MPPI_FLAG_FP_CONTRACT: fused multiply-adds; not bit-identical to the reference's rounding)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-subrecords", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-subrecords", action="store_true", help="(--full) skip the sub-records")
     ap.add_argument("--no-prelaunched", action="store_true", help="skip the opt-in pre-launched pipeline's figure (under rocprofv3 --pmc dispatches are serialised: the pipeline cannot form, every step runs into its 20 ms deadline and the figure is skipped anyway)")
     return ap.parse_args()
 
 
-def run_ranks(args, job_env, timeout_s, extra=()):
+def argv_without_dump(argv):
+    """argv without --dump-outputs DIR: the outputs of a run of several jobs are those of the first job that produced a line"""
+    out, skip = [], False
+    for a_ in argv:
+        if skip:
+            skip = False
+        elif a_ == "--dump-outputs":
+            skip = True
+        elif not a_.startswith("--dump-outputs="):
+            out.append(a_)
+    return out
+
+
+def run_ranks(args, job_env, timeout_s, extra=(), dump=True):
     """One child job: N ranks under torch.distributed.run with job_env (MPPI_EXCHANGE, MPPI_RCCL_CALL) set, at most timeout_s seconds.
     -> (parsed JSON line or None, outcome text). The child is its own process group: on a timeout exactly that group is
     killed (SIGTERM, then SIGKILL after 10 s). Nothing is ever re-exec'd and this process never touches a GPU."""
@@ -85,7 +116,8 @@ def run_ranks(args, job_env, timeout_s, extra=()):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: what RCCL and the hipIpc inboxes need on this pool
     env.update(job_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:] + list(extra)
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + \
+        (sys.argv[1:] if dump else argv_without_dump(sys.argv[1:])) + list(extra)
     sys.stderr.write("bench.py: %d ranks, %s, limit %d s\n" % (args.gpus, " ".join("%s=%s" % kv for kv in sorted(job_env.items())), timeout_s))
     sys.stderr.flush()
     with tempfile.TemporaryFile() as err:
@@ -186,7 +218,7 @@ def self_launch(args):
             continue
         # later jobs re-measure the headline only: the configs[4] sub-record (8 ms steps) does not depend on the exchange
         extra = ["--no-subrecords"] if got else []
-        line, outcome[name] = run_ranks(args, env, int(limit), extra)
+        line, outcome[name] = run_ranks(args, env, int(limit), extra, dump=not got)
         if line is not None:
             got[name] = line
             sys.stderr.write("bench.py: job %s: %s\n" % (name, json.dumps(line)))
@@ -224,7 +256,7 @@ def direct_exchange_in_children(args, world, rank, dist):
     for k in [k for k in env if k.startswith("TORCHELASTIC_")]:
         del env[k]  # (TORCHELASTIC_USE_AGENT_STORE would make the children look for the launcher's store on the new port)
     drop = {"--no-subrecords", "--no-cpu-baseline"}
-    cmd = [sys.executable, os.path.abspath(__file__)] + [a_ for a_ in sys.argv[1:] if a_ not in drop] + ["--no-subrecords", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + [a_ for a_ in argv_without_dump(sys.argv[1:]) if a_ not in drop] + ["--no-subrecords", "--no-cpu-baseline"]
     if rank == 0:
         sys.stderr.write("bench.py: the direct exchange in %d child processes, limit %d s\n" % (world, limit))
         sys.stderr.flush()
@@ -559,10 +591,13 @@ class Runner:
         dist.all_gather_into_tensor(out, t)
         return [float(q) for q in out.cpu()]
 
-    def run(self, workload, K, H, steps, warmup, min_time, **handle_kw):
-        """-> dict of measurements of one workload (K rollouts per rank)"""
+    def run(self, workload, K, H, steps, warmup, min_time, profile=True, outputs=False, settle_s=0.0, **handle_kw):
+        """-> dict of measurements of one workload (K rollouts per rank). profile: the kernel-duration pass after the timed steps;
+        outputs: the last timed step's u, action sequence and rollout costs under "outputs" (host fp32 arrays);
+        settle_s: seconds of steps before the warm-up, undone on the controller's state"""
         import numpy as np
         import torch
+        import mppi_tf_amd as m
         from mppi_tf_amd.distributed import ExchangeTimeout, ShardedController
         a, net = WORKLOADS[workload]
         mlp = mlp_of(workload)
@@ -602,6 +637,15 @@ class Runner:
                 ctl.resync()
             raise RuntimeError("the all-gather path cannot time out")
 
+        if settle_s > 0:
+            # a window that opens a few warm-up steps after start-up times the clocks' ramp (a 100-step run of the headline reads 13 % slow):
+            # the step first runs for settle_s seconds, then the controller gets back its initial state (U and the Philox step counter, what
+            # resync() restores), so that the W warm-up steps and the timed steps compute what they would on a fresh controller
+            U0, step0 = ctl.backend.action_sequence(), ctl.backend.step_counter()
+            t_settle = time.perf_counter()
+            while self.max_over_ranks(1.0 if time.perf_counter() - t_settle < settle_s else 0.0) > 0.0:
+                steps_timed(min(steps, 100))
+            ctl.backend.set_state(U0, step0)
         steps_timed(warmup)
         # batches of EXACTLY `steps` steps until --min-time seconds have been TIMED (a cap of 200 batches made the
         # driver's --steps 20 run 79 ms of GPU work, over before the clocks had settled). The cap is wall time (barriers and Python
@@ -614,38 +658,45 @@ class Runner:
             batches.append(steps_timed(steps))
         el = float(np.median(batches))
         rank_ms = [1e3 * q / steps for q in self.per_rank(rank_el[0])]  # each rank's own time for the last batch, before the barrier
-        # kernel durations: the same K steps with HIP events bound to each launch (the dispatches' own begin/end)
         h = ctl.backend.h
-        # >= 200 launches whatever --steps is (the driver's --steps 20 gave a 20-launch average, 10 % above steady state);
-        # the millisecond-scale learned-model steps keep their batch size (their kernels are long enough to be their own steady state)
-        n_prof = max(steps, 200) if el / steps < 1e-3 else steps
-        # The pass runs TWICE and the first is discarded: a HIP event is backed by a signal the runtime allocates when the event is first
-        # recorded, and a pass over fresh events starves the queue while it does — the first 200 event-bracketed launches of a handle read
-        # 16.4 us for the headline kernel, the second 200 15.6, every later pass 15.0 (tools/dbg_prof.py; r04's driver line: 17.32 against
-        # 15.79 under rocprofv3). Steady state is what the roofline is about.
-        for attempt in range(2 if el / steps < 1e-3 else 1):
-            h.profile_begin(n_prof)
-            if self.world == 1 and ctl.exchange == "none":
-                # the timed region keeps the GPU's queue full; so must this pass, or the kernels are timed on a GPU that idles between them
-                # (the Python frames of ShardedController.next cost more than an event-bracketed launch leaves): the handle directly
-                xp, up, sp = x.data_ptr(), ctl.u.data_ptr(), torch.cuda.current_stream(self.dev)
-                for _ in range(n_prof):
-                    h.next_device(xp, up, sp)
-            else:
-                for _ in range(n_prof):
-                    ctl.next(x)
-            torch.cuda.synchronize(self.dev)
-            roll_ms, fin_ms, n_done = h.profile_end()
-        n_prof = n_done
-        assert np.isfinite(ctl.u.cpu().numpy()).all(), "non-finite control after %d profiled steps of %s (exchange %s): u = %s, first record (beta, eta) = %s" % (
-            n_prof, workload, ctl.exchange, ctl.u.cpu().numpy(), ctl.records[:2].cpu().numpy())
+        outs = None
+        if outputs:  # what the last timed step handed its caller (steps_timed has synchronised the device)
+            outs = {"u": ctl.u.cpu().numpy().astype(np.float32), "action_sequence": ctl.backend.action_sequence().numpy().astype(np.float32),
+                    "costs": np.asarray(h.debug_get(m.DBG_COSTS), np.float32)}
+        roll_ms, fin_ms, n_prof = None, None, 0
+        if profile:
+            # kernel durations: the same K steps with HIP events bound to each launch (the dispatches' own begin/end)
+            # >= 200 launches whatever --steps is (the driver's --steps 20 gave a 20-launch average, 10 % above steady state);
+            # the millisecond-scale learned-model steps keep their batch size (their kernels are long enough to be their own steady state)
+            n_prof = max(steps, 200) if el / steps < 1e-3 else steps
+            # The pass runs TWICE and the first is discarded: a HIP event is backed by a signal the runtime allocates when the event is first
+            # recorded, and a pass over fresh events starves the queue while it does — the first 200 event-bracketed launches of a handle read
+            # 16.4 us for the headline kernel, the second 200 15.6, every later pass 15.0 (tools/dbg_prof.py; r04's driver line: 17.32 against
+            # 15.79 under rocprofv3). Steady state is what the roofline is about.
+            for attempt in range(2 if el / steps < 1e-3 else 1):
+                h.profile_begin(n_prof)
+                if self.world == 1 and ctl.exchange == "none":
+                    # the timed region keeps the GPU's queue full; so must this pass, or the kernels are timed on a GPU that idles between them
+                    # (the Python frames of ShardedController.next cost more than an event-bracketed launch leaves): the handle directly
+                    xp, up, sp = x.data_ptr(), ctl.u.data_ptr(), torch.cuda.current_stream(self.dev)
+                    for _ in range(n_prof):
+                        h.next_device(xp, up, sp)
+                else:
+                    for _ in range(n_prof):
+                        ctl.next(x)
+                torch.cuda.synchronize(self.dev)
+                roll_ms, fin_ms, n_done = h.profile_end()
+            n_prof = n_done
+        assert np.isfinite(ctl.u.cpu().numpy()).all(), "non-finite control after %d timed and %d profiled steps of %s (exchange %s): u = %s, first record (beta, eta) = %s" % (
+            steps * len(batches), n_prof, workload, ctl.exchange, ctl.u.cpu().numpy(), ctl.records[:2].cpu().numpy())
         bytes_ss, flop_ss = work_per_state_step(workload)
         state_steps = K * H
         res = {"workload": workload, "K_per_gpu": K, "H": H, "a_dim": a, "s_dim": cfg["s_dim"], "steps": steps, "batches_s": batches,
                "rollouts_per_s": K * self.world * steps / el, "ms_per_step": 1e3 * el / steps, "rank_ms_per_step": rank_ms,
                "kernel": h.rollout_kernel_name(), "kernel_ms_avg": roll_ms, "finish_kernel_ms_avg": fin_ms, "launches_timed": n_prof,
                "algorithmic_bytes_per_launch": bytes_ss * state_steps + 8 * K, "algorithmic_flop_per_launch": flop_ss * state_steps,
-               "exchange": ctl.exchange, "p2p_note": ctl.p2p_note, "rccl_note": ctl.rccl_note, "record_size": h.record_size, "mlp": mlp}
+               "exchange": ctl.exchange, "p2p_note": ctl.p2p_note, "rccl_note": ctl.rccl_note, "record_size": h.record_size, "mlp": mlp,
+               "outputs": outs}
         del ctl
         return res
 
@@ -785,15 +836,20 @@ def main():
     steps = args.steps if args.steps is not None else (20 if is_mlp else 200)
     rn = Runner(args, dev, world, rank, local_rank)
     head_kw = dict(mlp_bf16x3=True) if args.bf16x3 else (dict(fp_contract=True) if args.fp_contract else {})
-    r = rn.run(headline, K, H, steps, args.warmup if not is_mlp else min(args.warmup, 3), args.min_time, **head_kw)
+    r = rn.run(headline, K, H, steps, args.warmup if not is_mlp else min(args.warmup, 3), args.min_time or 0.0,
+               profile=args.full, outputs=bool(args.dump_outputs) and rank == 0, settle_s=SETTLE_S, **head_kw)
+    if r["outputs"] is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in r["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
     subs = []
-    if args.workload is None and not args.no_subrecords:
+    if args.full and args.workload is None and not args.no_subrecords:
         if world == 1:  # the other single-GPU BASELINE configs, so that one driver run measures them all
             # (sub-records are not the contract's "exactly K steps": their batches are at least 200 steps, so that the barrier + synchronize at both
             # ends of a batch — 20 us against a 9 us step — does not read as step time under the driver's --steps 20; the batch size is in the record)
             steps_sub = max(steps, 200)
-            subs.append(rn.run("pm2d", 4096, 64, steps_sub, args.warmup, args.min_time))
+            subs.append(rn.run("pm2d", 4096, 64, steps_sub, args.warmup, 1.0 if args.min_time is None else args.min_time))
             subs.append(rn.run("pm3d", 65536, 64, steps_sub, args.warmup, 0.3, fp_contract=True))  # MPPI_FLAG_FP_CONTRACT: the opt-in contracted instance
             subs.append(rn.run("mlp", 65536, 64, 20, 3, 0.0))
             subs.append(rn.run("mlp", 65536, 64, 20, 3, 0.0, mlp_bf16x3=True))
@@ -811,7 +867,7 @@ def main():
             subs.append(rn.run("pm3d" if rehearsal else "mlp", 65536, 128, 10, 2, 0.0))
 
     parity = None
-    if world > 1 or dist.is_initialized():
+    if args.full and (world > 1 or dist.is_initialized()):
         try:
             parity = sharded_parity(rn, headline, K, H)
             if not is_mlp and headline not in GEN:
@@ -839,8 +895,9 @@ def main():
                        "K_global": K * world, "K_per_gpu": K, "H": H, "s_dim": s_dim, "a_dim": a,
                        "lambda": float(cfg_of(headline, H).get("lam", 1.0)), "sigma": "1500*I (6 thrusts, N)" if a == 6 else "0.25*I", "dt": 0.1,
                        "parallelism": "K-shard x%d" % world, "exchange": r["exchange"], "record_floats": r["record_size"]},
-            "roofline": dict(roofline_of(r), code_sha=__import__("mppi_tf_amd").build.source_sha()),  # the kernel sources this run executed: tools/summarize_profiles.py tags the profile with it
         }
+        if args.full:
+            out["roofline"] = dict(roofline_of(r), code_sha=__import__("mppi_tf_amd").build.source_sha())  # the kernel sources this run executed: tools/summarize_profiles.py tags the profile with it
         if world > 1 or dist.is_initialized():
             out["rccl_ranks"] = dist.get_world_size() if dist.is_initialized() else 1
             if rehearsal:
@@ -856,7 +913,7 @@ def main():
                 out["sub_records"][0]["config"] = "configs[4]" if world == 8 else "configs[4] per-GPU shape, K=%d over %d GPUs" % (65536 * world, world)
                 out["sub_records"][0]["exchange"] = subs[0]["exchange"]
                 out["sub_records"][0]["rank_ms_per_step"] = [r4(q) for q in subs[0]["rank_ms_per_step"]]
-        if world == 1:
+        if world == 1 and args.full:
             out["ms_per_control_step_sync"] = sync_record(m, headline, H, K, r["mlp"], **head_kw)
             if not is_mlp and headline not in GEN and not head_kw and not args.no_prelaunched:
                 try:

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,8 +14,9 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
             "dtype", "data", "config", "roofline")
 
 
-def run_bench(*argv):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--min-time", "0", *argv],
+def run_bench(*argv, full=True):
+    extra = ("--min-time", "0", "--full") if full else ()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", *extra, *argv],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -41,6 +43,31 @@ def test_every_workload_prints_the_contract_line(workload, samples, horizon):
         assert "prelaunched" not in out["config"]["workload"]
     else:
         assert "prelaunched" not in out
+
+
+FULL_ONLY = ("roofline", "sub_records", "ms_per_control_step_sync", "prelaunched", "cpu_baseline", "parity")
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run is the headline alone: one batch of exactly --steps timed steps and none of --full's fields. --dump-outputs writes
+    what the last timed step computed, and two runs with the same arguments write the same arrays (seeded inputs, fixed-order finish)."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        out = run_bench("--workload", "pm3d", "--samples", "8192", "--horizon", "16", "--dump-outputs", str(d), full=False)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["steps"] == 3 and out["batches"]["n"] == 1 and out["ms_per_step"] > 0
+        assert abs(out["value"] - 8192 / (out["ms_per_step"] * 1e-3)) <= 0.02 * out["value"]
+        for key in FULL_ONLY:
+            assert key not in out, key
+        dumps.append({n: np.load(str(d / (n + ".npy"))) for n in ("u", "action_sequence", "costs")})
+    first = dumps[0]
+    assert first["u"].shape == (3,) and first["action_sequence"].shape == (16, 3) and first["costs"].shape == (8192,)
+    for n, arr in first.items():
+        assert arr.dtype == np.float32 and np.isfinite(arr).all(), n
+        np.testing.assert_array_equal(dumps[1][n], arr, err_msg=n)
+    assert np.abs(first["u"]).max() > 0 and np.ptp(first["costs"]) > 0
 
 
 @pytest.mark.parametrize("workload,extra", [("pm2d", []), ("auv", ["--samples", "4096", "--horizon", "8"]), ("nnspeed", ["--samples", "4096", "--horizon", "8"])])

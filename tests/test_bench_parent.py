@@ -61,3 +61,12 @@ def test_merge_keeps_the_parity_verdict_and_the_subrecords():
     assert "direct exchange not used" in line2["exchange"]["p2p"]["note"]
     assert line2["parity"]["measured_by"] == "rccl_torch" and line2["parity"]["ranks_bit_identical"] is True
     json.dumps(line); json.dumps(line2)
+
+
+def test_only_the_first_job_writes_the_outputs():
+    """--dump-outputs DIR reaches the first job of a multi-job run alone: later jobs (and the direct-exchange children) get argv without it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.argv_without_dump(["--gpus", "2", "--dump-outputs", "out", "--steps", "5"]) == ["--gpus", "2", "--steps", "5"]
+    assert bench.argv_without_dump(["--dump-outputs=out", "--full"]) == ["--full"]
+    assert bench.argv_without_dump(["--steps", "5"]) == ["--steps", "5"]

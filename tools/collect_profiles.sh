@@ -24,7 +24,7 @@ for SPEC in "$@"; do
   mkdir -p $D
   STEPS=100
   case $WL in mlp) STEPS=10;; mlp32|nnauv|auv|nnspeed) STEPS=30;; esac
-  BENCH="python3 $R/bench.py --workload $WL $EXTRA --steps $STEPS --warmup 3 --no-cpu-baseline --no-subrecords --no-prelaunched --min-time 0"
+  BENCH="python3 $R/bench.py --full --workload $WL $EXTRA --steps $STEPS --warmup 3 --no-cpu-baseline --no-subrecords --no-prelaunched --min-time 0"
   echo "== $NAME: $BENCH"
   # the stats pass times the kernel in steady state: batches repeated for 0.3 s, as bench.py's timed region does (a 100-step run alone is over
   # before the clocks have ramped: 18.1 us for the headline kernel against 15.7-16.0 us here, profiles/r04_philox_ab_rocprofv3.txt)

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/philox_ab_rocprof
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python3 $R/bench.py --workload pm3d --steps 200 --warmup 20 --no-cpu-baseline --no-subrecords --min-time 0.2"
+BENCH="python3 $R/bench.py --full --workload pm3d --steps 200 --warmup 20 --no-cpu-baseline --no-subrecords --min-time 0.2"
 for i in 1 2 3; do
   unset MPPI_SO_PATH
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/new$i -- $BENCH > $OUT/new$i.log 2>&1

@@ -402,6 +402,36 @@ mppi_status mppi_profile_end(mppi_handle *h, float *rollout_ms_avg, float *finis
  * (e.g. "mppi::k_rollout_pc<3, 3, 6, true, 0, 0>"): what a roofline figure of this handle refers to. */
 mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf, size_t n);
 
+/* ---- batched controllers: B independent MPPI problems stepped in the same two launches as one ------------------------------------
+ * A batched handle holds n >= 1 members that share ONE mppi_config (k, tau, dt, mass, lambda, gamma, upsilon, sigma, Q, the action-cost
+ * form, the action limits and the Philox step counter); each member has its own state, goal, action sequence (warm-started and shifted as
+ * a lone handle's) and Philox key. Member m is bit for bit the handle mppi_create makes from the same config with cfg.seed = seeds[m], fed
+ * the same x, goal and sequence on the same step counter: sample costs, U' and u. Members never interact.
+ * Serves the point-mass model (a_dim 1..4) with the quadratic state cost (diagonal or dense Q), either action-cost form, diagonal or dense
+ * sigma, action limits, every horizon the producer/consumer rollout takes (tau <= 160; <= 132 above 512 tiles), k <= 65536 per member.
+ * Refused with MPPI_ERR_UNSUPPORTED: the MLP / AUV / NNAUV / NNAUVSpeed models, the ellipse costs and StaticQuatCost, normalize_cost,
+ * MPPI_FLAG_FP_CONTRACT, MPPI_FLAG_MLP_BF16X3, shard_count > 1; on the handle the tunings MPPI_TUNE_FUSED_STEP != 0, _ARMED_US,
+ * _PRELAUNCH and _FORCE_TILE_KERNEL, the sequence filter and the transition log. The per-member entry points (mppi_next,
+ * mppi_next_with_noise, mppi_next_device, mppi_set_goal, mppi_get/set_action_sequence, mppi_debug_get, mppi_shard_*, the log and CSV
+ * calls) refuse a batched handle with MPPI_ERR_UNSUPPORTED; mppi_destroy, mppi_synchronize, mppi_set_action_limits,
+ * mppi_get/set_step_counter, mppi_profile_begin/end and mppi_rollout_kernel_name serve it as they serve a plain one. Sizes that do not
+ * match, n < 1 and a member out of range are MPPI_ERR_INVALID_ARG. */
+/* n members; seeds[n] their Philox keys (NULL: cfg->seed + m); every goal starts as cfg->goal, every sequence as zeros */
+mppi_status mppi_create_batch(const mppi_config *cfg, int n, const uint64_t *seeds, mppi_handle **out);
+/* the member count B; 0 for a plain handle */
+int mppi_batch_size(const mppi_handle *h);
+/* goals[B, s] (n = B*s_dim): every member's goal (setGoal per member) */
+mppi_status mppi_batch_set_goals(mppi_handle *h, const float *goals, int n);
+/* one step of every member, synchronous: x[B, s] (n_x = B*s_dim) -> u_out[B, a] (n_u = B*a_dim) */
+mppi_status mppi_batch_next(mppi_handle *h, const float *x, int n_x, float *u_out, int n_u);
+/* the same, enqueue only: x_dev[B, s] -> u_dev[B, a] on `stream` (NULL = the handle's own; the convention of mppi_next_device) */
+mppi_status mppi_batch_next_device(mppi_handle *h, const float *x_dev, float *u_dev, void *stream);
+/* every member's nominal sequence U[B, tau, a] (n = B*tau*a_dim); set resets the warm start as mppi_set_action_sequence does */
+mppi_status mppi_batch_get_action_sequences(mppi_handle *h, float *U, int n);
+mppi_status mppi_batch_set_action_sequences(mppi_handle *h, const float *U, int n);
+/* mppi_debug_get of ONE member (MPPI_DBG_*, the sizes of a lone handle); MPPI_DBG_NOISE regenerates the member's noise from seeds[member] */
+mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what, float *out, size_t n);
+
 /* ---- the learner of the learned model_base (replaces LearnerBase.train / _train_step, learners/learner_base.py:324-358,
  * 469-496; train_all :146-153) --------------------------------------------------------------------------------------------
  * Full-batch Adam on the mean squared error of the network's prediction against the (normalised) targets, for the

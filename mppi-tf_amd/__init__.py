@@ -5,7 +5,7 @@ model H steps, cost every step, soft-min weight, reduce to the new nominal seque
 hand-written HIP for gfx950 in csrc/, reached through the C-ABI of include/mppi_c.h.
 
   csrc/            HIP kernels + the C-ABI implementation  -> libmppi_hip.so (build.py)
-  _lib.py          ctypes binding (Handle)
+  _lib.py          ctypes binding (Handle; BatchHandle: B controllers stepped together)
   controller.py    the reference's ControllerBase / StaticCost / PointMassModel interface
   auv.py           the 13-state family: AUVModel, NNAUVModel, NNAUVModelSpeed, StaticQuatCost, ElipseCost3D
   learner.py       LearnerBase: replay buffer + full-batch Adam on the GPU (csrc/mppi_learner.hip) -> the learned model's weights
@@ -13,12 +13,12 @@ hand-written HIP for gfx950 in csrc/, reached through the C-ABI of include/mppi_
 """
 from . import build as _build  # noqa: F401
 from ._lib import (ACTION_COST_CPP, ACTION_COST_PY, CSV_REFERENCE, CSV_ROUNDTRIP, DBG_AUX, DBG_BETA, DBG_COSTS, DBG_ETA, DBG_NOISE,
-                   DBG_U_UPDATED, DBG_WEIGHTS, Handle, MppiError, load)
+                   DBG_U_UPDATED, DBG_WEIGHTS, BatchHandle, Handle, MppiError, load)
 from .controller import ControllerBase, ControllerBaseCpp, CostBase, ElipseCost, PointMassModel, StaticCost
 from .auv import AUVModel, ElipseCost3D, NNAUVModel, NNAUVModelSpeed, StaticQuatCost
 from .learner import LearnerBase
 from ._lib import Learner
 
-__all__ = ["Handle", "MppiError", "load", "ControllerBase", "ControllerBaseCpp", "CostBase", "PointMassModel",
+__all__ = ["Handle", "BatchHandle", "MppiError", "load", "ControllerBase", "ControllerBaseCpp", "CostBase", "PointMassModel",
            "StaticCost", "ElipseCost", "AUVModel", "NNAUVModel", "NNAUVModelSpeed", "StaticQuatCost", "ElipseCost3D", "LearnerBase", "Learner", "ACTION_COST_CPP", "ACTION_COST_PY", "DBG_COSTS", "DBG_BETA", "DBG_ETA", "DBG_WEIGHTS",
            "DBG_NOISE", "DBG_U_UPDATED", "DBG_AUX", "CSV_REFERENCE", "CSV_ROUNDTRIP"]

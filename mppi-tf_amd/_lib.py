@@ -123,6 +123,15 @@ SIGNATURES = {
     "mppi_profile_begin": (C.c_int, [_H, C.c_int]),
     "mppi_profile_end": (C.c_int, [_H, FP, FP, C.POINTER(C.c_int)]),
     "mppi_rollout_kernel_name": (C.c_int, [_H, C.c_char_p, C.c_size_t]),
+    # batched controllers (BatchHandle)
+    "mppi_create_batch": (C.c_int, [C.POINTER(Config), C.c_int, C.POINTER(C.c_uint64), C.POINTER(_H)]),
+    "mppi_batch_size": (C.c_int, [_H]),
+    "mppi_batch_set_goals": (C.c_int, [_H, FP, C.c_int]),
+    "mppi_batch_next": (C.c_int, [_H, FP, C.c_int, FP, C.c_int]),
+    "mppi_batch_next_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mppi_batch_get_action_sequences": (C.c_int, [_H, FP, C.c_int]),
+    "mppi_batch_set_action_sequences": (C.c_int, [_H, FP, C.c_int]),
+    "mppi_batch_debug_get": (C.c_int, [_H, C.c_int, C.c_int, FP, C.c_size_t]),
     # the learner (LearnerBase.train / _train_step)
     "mppi_learner_create": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(FP), C.POINTER(FP), C.c_int, C.POINTER(_H)]),
     "mppi_learner_destroy": (None, [_H]),
@@ -552,6 +561,139 @@ class Handle:
 
     def profile_end(self):
         """-> (rollout kernel ms avg, finish kernel ms avg, steps recorded); HIP events on the launch stream."""
+        r, f, n = C.c_float(0), C.c_float(0), C.c_int(0)
+        self._check(self.lib.mppi_profile_end(self.h, C.byref(r), C.byref(f), C.byref(n)))
+        return r.value, f.value, n.value
+
+
+class BatchHandle:
+    """RAII wrapper of a batched mppi_handle (mppi_create_batch): n independent controllers that share one configuration and step in the
+    same two launches. Member m is bit for bit Handle(..., seed=seeds[m]) fed the same x, goal and sequence (include/mppi_c.h)."""
+
+    def __init__(self, n, k, tau, s_dim, a_dim, dt=0.1, mass=1.0, lam=1.0, gamma=1.0, upsilon=1.0, sigma=None, goal=None, goals=None,
+                 Q=None, q_is_full=None, action_cost=ACTION_COST_CPP, seed=1, seeds=None, device=0, upsilon_scales_noise=False, tuning=None):
+        """n members; seeds: n Philox keys (None: seed + m); goal: every member's goal, goals: [n, s_dim] per member (after goal);
+        the other keywords as Handle's. tuning: dict of diagnostic switches (keys of TUNING) that a batch takes."""
+        lib = self.lib = load()
+        self.h = _H()
+        cfg = Config()
+        self._check(lib.mppi_config_init(C.byref(cfg), k, tau, dt, mass, s_dim, a_dim), None)
+        cfg.lam, cfg.gamma, cfg.upsilon, cfg.action_cost_kind = lam, gamma, upsilon, action_cost
+        cfg.seed, cfg.device, cfg.flags = seed, device, (1 if upsilon_scales_noise else 0)
+        keep = []
+        if sigma is not None:
+            keep.append(f32(sigma, (a_dim, a_dim)))
+            cfg.sigma = fp(keep[-1])
+        if goal is not None:
+            keep.append(f32(goal, (s_dim,)))
+            cfg.goal = fp(keep[-1])
+        if Q is not None:
+            q = f32(Q)
+            if q_is_full is None:
+                q_is_full = q.ndim == 2
+            keep.append(f32(q, (s_dim, s_dim) if q_is_full else (s_dim,)))
+            cfg.Q, cfg.q_is_full = fp(keep[-1]), int(q_is_full)
+        sp = None
+        if seeds is not None:
+            sv = np.ascontiguousarray(seeds, np.uint64).ravel()
+            if sv.size != n:
+                raise MppiError(ERR_INVALID_ARG, "seeds must hold n values")
+            keep.append(sv)
+            sp = sv.ctypes.data_as(C.POINTER(C.c_uint64))
+        self.n, self.k, self.tau, self.s, self.a = n, k, tau, s_dim, a_dim
+        st = lib.mppi_create_batch(C.byref(cfg), int(n), sp, C.byref(self.h))
+        if st != OK:
+            self.h = _H()
+            self._check(st, None)
+        self.k_local = lib.mppi_local_samples(self.h)
+        for key, val in (tuning or {}).items():
+            self.set_tuning(key, val)
+        if goals is not None:
+            self.set_goals(goals)
+
+    def _check(self, st, h=True):
+        if st != OK:
+            txt = self.lib.mppi_last_error(self.h if (h and self.h) else None) or b""
+            raise MppiError(st, "%s (%s)" % (txt.decode(), self.lib.mppi_status_string(st).decode()))
+
+    def close(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            self.lib.mppi_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_tuning(self, key, value):
+        self._check(self.lib.mppi_set_tuning(self.h, TUNING[key], int(value)))
+
+    def set_goals(self, goals):
+        g = f32(goals).ravel()
+        self._check(self.lib.mppi_batch_set_goals(self.h, fp(g), g.size))
+
+    def next(self, X):
+        """X [n, s_dim] -> u [n, a_dim] (synchronous)"""
+        x = f32(X).ravel()
+        u = np.zeros((self.n, self.a), np.float32)
+        self._check(self.lib.mppi_batch_next(self.h, fp(x), x.size, fp(u), u.size))
+        return u
+
+    def next_device(self, x_ptr, u_ptr, stream=None):
+        """x_ptr [n, s_dim] -> u_ptr [n, a_dim], device pointers; enqueue only (stream: Handle.next_device's convention)"""
+        self._check(self.lib.mppi_batch_next_device(self.h, x_ptr, u_ptr, Handle._stream(stream)))
+
+    def get_action_sequences(self):
+        U = np.zeros((self.n, self.tau, self.a), np.float32)
+        self._check(self.lib.mppi_batch_get_action_sequences(self.h, fp(U), U.size))
+        return U
+
+    def set_action_sequences(self, U):
+        U = f32(U).ravel()
+        self._check(self.lib.mppi_batch_set_action_sequences(self.h, fp(U), U.size))
+
+    def debug_get(self, member, what):
+        n = {DBG_COSTS: self.k_local, DBG_BETA: 1, DBG_ETA: 1, DBG_WEIGHTS: self.k_local,
+             DBG_NOISE: self.k_local * self.tau * self.a, DBG_U_UPDATED: self.tau * self.a, DBG_AUX: 8}[what]
+        out = np.zeros(n, np.float32)
+        self._check(self.lib.mppi_batch_debug_get(self.h, int(member), what, fp(out), n))
+        if what == DBG_NOISE:
+            return out.reshape(self.k_local, self.tau, self.a)
+        if what == DBG_U_UPDATED:
+            return out.reshape(self.tau, self.a)
+        return out if n > 1 else out[0]
+
+    def get_step_counter(self):
+        v = C.c_uint64(0)
+        self._check(self.lib.mppi_get_step_counter(self.h, C.byref(v)))
+        return int(v.value)
+
+    def set_step_counter(self, step):
+        self._check(self.lib.mppi_set_step_counter(self.h, step))
+
+    def set_action_limits(self, a_min=None, a_max=None):
+        """clip_act on every member (the limits are shared); None, None = off"""
+        if a_min is None and a_max is None:
+            self._check(self.lib.mppi_set_action_limits(self.h, None, None, 0))
+            return
+        lo, hi = f32(a_min, (self.a,)), f32(a_max, (self.a,))
+        self._check(self.lib.mppi_set_action_limits(self.h, fp(lo), fp(hi), self.a))
+
+    def synchronize(self):
+        self._check(self.lib.mppi_synchronize(self.h))
+
+    def rollout_kernel_name(self):
+        buf = C.create_string_buffer(128)
+        self._check(self.lib.mppi_rollout_kernel_name(self.h, buf, 128))
+        return buf.value.decode()
+
+    def profile_begin(self, max_steps):
+        self._check(self.lib.mppi_profile_begin(self.h, max_steps))
+
+    def profile_end(self):
+        """-> (batched rollout kernel ms avg, batched finish kernel ms avg, steps recorded)"""
         r, f, n = C.c_float(0), C.c_float(0), C.c_int(0)
         self._check(self.lib.mppi_profile_end(self.h, C.byref(r), C.byref(f), C.byref(n)))
         return r.value, f.value, n.value

@@ -135,6 +135,12 @@ static hipError_t quiesce(mppi_handle *h)
         HIP_TRY(h, quiesce(h));                      \
     } while (0)
 
+// a batched handle (mppi_create_batch) has no single x, goal or sequence: the per-member entry points refuse it (mppi_batch_* serve it)
+#define MPPI_NOT_BATCH(h, name)                                                                                                       \
+    do {                                                                                                                              \
+        if ((h) && (h)->batch) return fail((h), MPPI_ERR_UNSUPPORTED, std::string(name) + ": a batched handle steps through mppi_batch_*"); \
+    } while (0)
+
 // ----------------------------------------------------------------------------------------
 extern "C" int mppi_abi_version(void) { return MPPI_ABI_VERSION; }
 extern "C" const char *mppi_version(void) { return MPPI_VERSION_STRING; }
@@ -230,6 +236,8 @@ extern "C" void mppi_destroy(mppi_handle *h)
                      h->d_record, h->d_dbg, h->d_mm, h->d_eps, h->d_recs, h->d_range, h->d_tile_mm};
     for (float *p : bufs) if (p) (void)hipFree(p);
     if (h->d_step) (void)hipFree(h->d_step);
+    if (h->d_seeds) (void)hipFree(h->d_seeds);
+    for (float *p : {h->d_goals, h->d_bx, h->d_bu}) if (p) (void)hipFree(p);
     if (h->dM) (void)hipFree(h->dM);
     if (h->d_mlp_w) (void)hipFree(h->d_mlp_w);
     if (h->dC) (void)hipFree(h->dC);
@@ -701,6 +709,7 @@ extern "C" mppi_status mppi_set_action_limits(mppi_handle *h, const float *a_min
 
 extern "C" mppi_status mppi_set_sequence_filter(mppi_handle *h, int window, int polyorder)
 {
+    MPPI_NOT_BATCH(h, "mppi_set_sequence_filter");
     if (!h) return MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h);
     HIP_TRY(h, hipDeviceSynchronize());
@@ -829,7 +838,9 @@ extern "C" mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf,
 {
     if (!h || !buf || n == 0) return MPPI_ERR_INVALID_ARG;
     const int NG = (h->H + 3) / 4;
-    if (h->is_gen) std::snprintf(buf, n, "%s", mppi_gen_kernel_name(h));
+    if (h->batch) std::snprintf(buf, n, "mppi::k_rollout_pc_batch<%d, %d, %d, %s, %d>", h->a, h->pc_np,
+                                h->pc_np == 3 ? (NG <= 18 ? 6 : 11) : (NG <= 20 ? 4 : 8), h->sigma_diag ? "true" : "false", h->hc.q_full ? 2 : 0);
+    else if (h->is_gen) std::snprintf(buf, n, "%s", mppi_gen_kernel_name(h));
     else if (h->hc.model_kind == MPPI_MODEL_MLP)
         if (h->mlp_small == 32 && h->mlp_bx3) std::snprintf(buf, n, "mppi::k_rollout_mlp32_bx3<%d>", h->a);
         else if (h->mlp_small == 32 && h->mlp32_valu == 0) std::snprintf(buf, n, "mppi::k_rollout_mlp32_pc<%d, %s>", h->a, h->sigma_diag ? "true" : "false");
@@ -892,6 +903,7 @@ extern "C" mppi_status mppi_profile_end(mppi_handle *h, float *rollout_ms_avg, f
 
 extern "C" mppi_status mppi_set_goal(mppi_handle *h, const float *goal, int n)
 {
+    MPPI_NOT_BATCH(h, "mppi_set_goal");
     if (!h) return MPPI_ERR_INVALID_ARG;
     if (!goal || n != h->s) // "Wrong goal size, it should match the state dimension" controller_base.cpp:127-130
         return fail(h, MPPI_ERR_INVALID_ARG, "wrong goal size, it should match the state dimension");
@@ -1043,6 +1055,7 @@ static mppi_status pre_step(mppi_handle *h, const float *x_dev, float *u_dev)
 
 extern "C" mppi_status mppi_next_device(mppi_handle *h, const float *x_dev, float *u_dev, void *stream)
 {
+    MPPI_NOT_BATCH(h, "mppi_next_device");
     if (!h || !x_dev || !u_dev) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL device pointer") : MPPI_ERR_INVALID_ARG;
     if (h->shard_count != 1) return fail(h, MPPI_ERR_INVALID_ARG, "sharded handle: use mppi_shard_partial / mppi_shard_finish");
     if (stream == nullptr && pre_ok(h)) return pre_step(h, x_dev, u_dev);
@@ -1060,6 +1073,7 @@ extern "C" mppi_status mppi_next_device(mppi_handle *h, const float *x_dev, floa
 
 extern "C" mppi_status mppi_shard_partial(mppi_handle *h, const float *x_dev, float *record_dev, void *stream)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_partial");
     if (!h || !x_dev || !record_dev) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL device pointer") : MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h);
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -1086,6 +1100,7 @@ static bool norm_fast(const mppi_handle *h)
 
 extern "C" mppi_status mppi_shard_cost_range(mppi_handle *h, const float *x_dev, float *range_dev, void *stream)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_cost_range");
     if (!h || !x_dev || !range_dev) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL device pointer") : MPPI_ERR_INVALID_ARG;
     if (!h->normalize) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_shard_cost_range: the handle was created without normalize_cost");
     MPPI_ENTER(h);
@@ -1105,6 +1120,7 @@ extern "C" mppi_status mppi_shard_cost_range(mppi_handle *h, const float *x_dev,
 
 extern "C" mppi_status mppi_shard_partial_normalized(mppi_handle *h, const float *x_dev, const float *range_dev, float *record_dev, void *stream)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_partial_normalized");
     if (!h || !x_dev || !range_dev || !record_dev) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL device pointer") : MPPI_ERR_INVALID_ARG;
     if (!h->normalize) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_shard_partial_normalized: the handle was created without normalize_cost");
     MPPI_ENTER(h);
@@ -1133,6 +1149,7 @@ extern "C" mppi_status mppi_shard_partial_normalized(mppi_handle *h, const float
 
 extern "C" mppi_status mppi_shard_finish(mppi_handle *h, const float *records_dev, int n_records, float *u_dev, void *stream)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_finish");
     if (!h || !records_dev || !u_dev || n_records <= 0) return h ? fail(h, MPPI_ERR_INVALID_ARG, "bad records/u pointer or count") : MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h);
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -1144,6 +1161,7 @@ extern "C" mppi_status mppi_shard_finish(mppi_handle *h, const float *records_de
 // One call per sharded step on the collective path (include/mppi_c.h): record -> the caller's all-gather (in place) -> finish.
 extern "C" mppi_status mppi_shard_step(mppi_handle *h, const float *x_dev, float *u_dev, const mppi_collectives *coll, void *stream)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_step");
     if (!h || !x_dev || !u_dev) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL device pointer") : MPPI_ERR_INVALID_ARG;
     const bool gather = coll && coll->all_gather;
     if (h->shard_count > 1 && !gather) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_shard_step: shard_count > 1 needs coll->all_gather (ncclAllGather's signature)");
@@ -1177,6 +1195,7 @@ extern "C" mppi_status mppi_shard_step(mppi_handle *h, const float *x_dev, float
 // ---- direct record exchange (see include/mppi_c.h) -----------------------------------------------
 extern "C" mppi_status mppi_shard_p2p_export(mppi_handle *h, void *ipc_handle_out, void **inbox_dev_out)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_p2p_export");
     if (!h || !inbox_dev_out) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL inbox_dev_out") : MPPI_ERR_INVALID_ARG;
     if (h->shard_count > kMaxPeers) return fail(h, MPPI_ERR_UNSUPPORTED, "direct exchange supports at most 16 shards");
     // fault injection for the fallback tests: mppi_set_tuning(MPPI_TUNE_P2P_FAULT, 1 = export | 2 = probe)
@@ -1206,6 +1225,7 @@ extern "C" mppi_status mppi_shard_p2p_export(mppi_handle *h, void *ipc_handle_ou
 
 extern "C" mppi_status mppi_shard_p2p_open(mppi_handle *h, const void *ipc_handle, void **peer_inbox_out)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_p2p_open");
     if (!h || !ipc_handle || !peer_inbox_out) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL ipc handle / output") : MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h);
     hipIpcMemHandle_t ih;
@@ -1219,6 +1239,7 @@ extern "C" mppi_status mppi_shard_p2p_open(mppi_handle *h, const void *ipc_handl
 
 extern "C" mppi_status mppi_shard_p2p_attach(mppi_handle *h, void *const *inboxes, int n, int timeout_ms)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_p2p_attach");
     if (!h || !inboxes) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL inbox table") : MPPI_ERR_INVALID_ARG;
     if (n != h->shard_count || n > kMaxPeers) return fail(h, MPPI_ERR_INVALID_ARG, "need exactly shard_count (<= 16) inbox pointers, rank order");
     if (!h->xchg_inbox) return fail(h, MPPI_ERR_INVALID_ARG, "call mppi_shard_p2p_export first");
@@ -1235,6 +1256,7 @@ extern "C" mppi_status mppi_shard_p2p_attach(mppi_handle *h, void *const *inboxe
 
 extern "C" mppi_status mppi_shard_p2p_probe(mppi_handle *h, void *stream, int *ok_out)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_p2p_probe");
     if (!h || !ok_out) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL ok_out") : MPPI_ERR_INVALID_ARG;
     if (!h->xchg_attached) return fail(h, MPPI_ERR_INVALID_ARG, "inboxes not attached");
     MPPI_ENTER(h);
@@ -1257,6 +1279,7 @@ extern "C" mppi_status mppi_shard_p2p_probe(mppi_handle *h, void *stream, int *o
 
 extern "C" mppi_status mppi_shard_p2p_step(mppi_handle *h, const float *x_dev, float *u_dev, void *stream)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_p2p_step");
     if (!h || !x_dev || !u_dev) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL device pointer") : MPPI_ERR_INVALID_ARG;
     if (!h->xchg_attached) return fail(h, MPPI_ERR_INVALID_ARG, "inboxes not attached");
     // a deadline missed by any earlier step: refuse (the steps enqueued since then applied zero updates; U and the step
@@ -1276,6 +1299,7 @@ extern "C" mppi_status mppi_shard_p2p_step(mppi_handle *h, const float *x_dev, f
 
 extern "C" mppi_status mppi_shard_p2p_status(mppi_handle *h, int *timed_out)
 {
+    MPPI_NOT_BATCH(h, "mppi_shard_p2p_status");
     if (!h || !timed_out) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL timed_out") : MPPI_ERR_INVALID_ARG;
     *timed_out = h->h_xchg_status ? (int)(*(volatile unsigned *)h->h_xchg_status & 1u) : 0;
     return MPPI_OK;
@@ -1297,6 +1321,7 @@ static long long now_ns()
 static mppi_status step_host(mppi_handle *h, const float *x, int n_x, const float *eps, size_t n_eps, float *u_out, int n_u)
 {
     if (!h) return MPPI_ERR_INVALID_ARG;
+    MPPI_NOT_BATCH(h, eps ? "mppi_next_with_noise" : "mppi_next");
     if (!x || !u_out || n_x != h->s || n_u != h->a) return fail(h, MPPI_ERR_INVALID_ARG, "x must have s_dim floats and u_out a_dim floats");
     if (h->shard_count != 1) return fail(h, MPPI_ERR_INVALID_ARG, "sharded handle: use mppi_shard_partial / mppi_shard_finish");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1431,6 +1456,7 @@ extern "C" mppi_status mppi_next_with_noise(mppi_handle *h, const float *x, int 
 
 extern "C" mppi_status mppi_set_transition_log(mppi_handle *h, int max_rows)
 {
+    MPPI_NOT_BATCH(h, "mppi_set_transition_log");
     if (!h) return MPPI_ERR_INVALID_ARG;
     if (max_rows < 0) return fail(h, MPPI_ERR_INVALID_ARG, "max_rows must be >= 0");
     try {
@@ -1445,6 +1471,7 @@ extern "C" mppi_status mppi_set_transition_log(mppi_handle *h, int max_rows)
 
 extern "C" mppi_status mppi_transition_log_stats(mppi_handle *h, uint64_t *rows_held, uint64_t *rows_overwritten, uint64_t *rows_without_successor)
 {
+    MPPI_NOT_BATCH(h, "mppi_transition_log_stats");
     if (!h) return MPPI_ERR_INVALID_ARG;
     size_t open_rows = 0;
     for (size_t q = 0; q < h->log_count; ++q)
@@ -1457,6 +1484,7 @@ extern "C" mppi_status mppi_transition_log_stats(mppi_handle *h, uint64_t *rows_
 
 extern "C" mppi_status mppi_save_next(mppi_handle *h, const float *x_next, int n)
 {
+    MPPI_NOT_BATCH(h, "mppi_save_next");
     if (!h) return MPPI_ERR_INVALID_ARG;
     if (!x_next || n != h->s) return fail(h, MPPI_ERR_INVALID_ARG, "x_next must have s_dim floats");
     if (!h->log_cap) return MPPI_OK; // logging is off
@@ -1475,6 +1503,7 @@ extern "C" mppi_status mppi_save_next(mppi_handle *h, const float *x_next, int n
 // = "%f" (6 decimals). MPPI_CSV_ROUNDTRIP writes "%.9g" (fp32 round-trips) without the trailing comma.
 extern "C" mppi_status mppi_to_csv_format(mppi_handle *h, const char *filename, int format)
 {
+    MPPI_NOT_BATCH(h, "mppi_to_csv_format");
     if (!h || !filename) return h ? fail(h, MPPI_ERR_INVALID_ARG, "filename is NULL") : MPPI_ERR_INVALID_ARG;
     if (format != MPPI_CSV_REFERENCE && format != MPPI_CSV_ROUNDTRIP) return fail(h, MPPI_ERR_INVALID_ARG, "unknown CSV format");
     if (!h->log_cap) return fail(h, MPPI_ERR_INVALID_ARG, "the transition log is off: call mppi_set_transition_log first");
@@ -1509,6 +1538,13 @@ extern "C" mppi_status mppi_set_tuning(mppi_handle *h, int what, int value)
 {
     if (!h) return MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h); // (an armed launch was built for the handle as it was)
+    if (h->batch) { // a batch always takes the two launches of mppi_launch_batch.hip
+        const char *why = (what == MPPI_TUNE_FUSED_STEP && value != 0) ? "fused_step"
+                        : (what == MPPI_TUNE_ARMED_US && value != 0) ? "armed_us"
+                        : (what == MPPI_TUNE_PRELAUNCH && value != 0) ? "prelaunch"
+                        : (what == MPPI_TUNE_FORCE_TILE_KERNEL && value != 0) ? "force_tile_kernel" : nullptr;
+        if (why) return fail(h, MPPI_ERR_UNSUPPORTED, std::string("tuning ") + why + ": a batched handle always runs the two-launch batched step");
+    }
     switch (what) {
     case MPPI_TUNE_FUSED_STEP:
         if (value < 0 || value > 2) return fail(h, MPPI_ERR_INVALID_ARG, "fused step: 0 (two launches), 1 (one launch), 2 (one launch, the six-wave workgroup at every horizon)");
@@ -1563,6 +1599,7 @@ extern "C" mppi_status mppi_set_tuning(mppi_handle *h, int what, int value)
 // ----------------------------------------------------------------------------------------
 extern "C" mppi_status mppi_get_action_sequence(mppi_handle *h, float *U, int n)
 {
+    MPPI_NOT_BATCH(h, "mppi_get_action_sequence");
     if (!h) return MPPI_ERR_INVALID_ARG;
     if (!U || n != h->HA) return fail(h, MPPI_ERR_INVALID_ARG, "U must hold tau*a floats");
     MPPI_ENTER(h);
@@ -1573,6 +1610,7 @@ extern "C" mppi_status mppi_get_action_sequence(mppi_handle *h, float *U, int n)
 
 extern "C" mppi_status mppi_set_action_sequence(mppi_handle *h, const float *U, int n)
 {
+    MPPI_NOT_BATCH(h, "mppi_set_action_sequence");
     if (!h) return MPPI_ERR_INVALID_ARG;
     if (!U || n != h->HA) return fail(h, MPPI_ERR_INVALID_ARG, "U must hold tau*a floats");
     MPPI_ENTER(h);
@@ -1606,6 +1644,7 @@ extern "C" mppi_status mppi_set_step_counter(mppi_handle *h, uint64_t step)
 
 extern "C" mppi_status mppi_debug_get(mppi_handle *h, int what, float *out, size_t n)
 {
+    MPPI_NOT_BATCH(h, "mppi_debug_get");
     if (!h || !out) return h ? fail(h, MPPI_ERR_INVALID_ARG, "out is NULL") : MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h);
     const size_t K = (size_t)h->K_local;
@@ -1878,5 +1917,253 @@ extern "C" mppi_status mppi_shift(const float *U, int tau, int a, const float *i
     int o = 0;
     for (int i = nb * a; i < tau * a; ++i) out[o++] = U[i];
     for (int i = 0; i < nb_init * a; ++i) out[o++] = init ? init[i] : 0.0f; // mInit0: zeros
+    return MPPI_OK;
+}
+
+// ---- batched controllers (mppi_create_batch; kernels in mppi_launch_batch.hip) ----------------------------------------------------
+// B members share one mppi_config; each has its own x, goal, sequence and Philox key. Member m is bit for bit the lone handle made from the
+// same config with cfg.seed = seeds[m], fed the same x, goal and sequence, on the same step counter: the batched rollout is the text of
+// k_rollout_pc with per-member operands, with the instance (producers, slots) that handle would launch, and the batched finish is
+// k_finish_cols' column_combine on the member's records over the same padded record count.
+static hipError_t launch_batch(mppi_handle *h, hipStream_t st, const float *x_dev)
+{
+    switch (h->a) {
+    case 1: return mppi_launch_batch_a1(h, st, x_dev);
+    case 2: return mppi_launch_batch_a2(h, st, x_dev);
+    case 3: return mppi_launch_batch_a3(h, st, x_dev);
+    case 4: return mppi_launch_batch_a4(h, st, x_dev);
+    }
+    return hipErrorInvalidValue;
+}
+
+static hipError_t launch_batch_finish(mppi_handle *h, hipStream_t st, float *u_dev, hipEvent_t ev0, hipEvent_t ev1)
+{
+    switch (h->a) {
+    case 1: return mppi_launch_batch_finish_a1(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
+    case 2: return mppi_launch_batch_finish_a2(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
+    case 3: return mppi_launch_batch_finish_a3(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
+    case 4: return mppi_launch_batch_finish_a4(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
+    }
+    return hipErrorInvalidValue;
+}
+
+// why cfg cannot be batched (NULL: it can, as far as the config alone tells)
+static const char *batch_refusal(const mppi_config *cfg)
+{
+    switch (cfg->model_kind) {
+    case MPPI_MODEL_POINT_MASS: break;
+    case MPPI_MODEL_MLP: return "batched controllers: model MLP is not supported (the point-mass model only)";
+    case MPPI_MODEL_AUV: return "batched controllers: model AUV is not supported (the point-mass model only)";
+    case MPPI_MODEL_NN_AUV: return "batched controllers: model NNAUV is not supported (the point-mass model only)";
+    case MPPI_MODEL_NN_AUV_SPEED: return "batched controllers: model NNAUVSpeed is not supported (the point-mass model only)";
+    default: break; // (mppi_create reports it)
+    }
+    switch (cfg->state_cost_kind) {
+    case MPPI_STATE_COST_QUADRATIC: break;
+    case MPPI_STATE_COST_ELLIPSE: return "batched controllers: the ellipse cost (ElipseCost) is not supported (the quadratic cost only)";
+    case MPPI_STATE_COST_ELLIPSE3D: return "batched controllers: the ellipse cost (ElipseCost3D) is not supported (the quadratic cost only)";
+    case MPPI_STATE_COST_QUAT: return "batched controllers: StaticQuatCost is not supported (the quadratic cost only)";
+    default: break;
+    }
+    if (cfg->normalize_cost) return "batched controllers: normalize_cost is not supported";
+    if (cfg->flags & MPPI_FLAG_FP_CONTRACT) return "batched controllers: MPPI_FLAG_FP_CONTRACT is not supported";
+    if (cfg->flags & MPPI_FLAG_MLP_BF16X3) return "batched controllers: MPPI_FLAG_MLP_BF16X3 is not supported";
+    if (cfg->shard_count > 1) return "batched controllers: sharding (shard_count > 1) is not supported";
+    return nullptr;
+}
+
+extern "C" mppi_status mppi_create_batch(const mppi_config *cfg, int n, const uint64_t *seeds, mppi_handle **out)
+{
+    if (!cfg || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfg/out is NULL");
+    *out = nullptr;
+    if (n < 1) return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: n must be >= 1");
+    if (cfg->struct_size != sizeof(mppi_config)) return fail(nullptr, MPPI_ERR_INVALID_ARG, "mppi_config.struct_size mismatch (use mppi_config_init)");
+    if (const char *why = batch_refusal(cfg)) return fail(nullptr, MPPI_ERR_UNSUPPORTED, why);
+    mppi_handle *h = nullptr;
+    if (mppi_status st = mppi_create(cfg, &h); st != MPPI_OK) return st;
+    auto refuse = [&](mppi_status st, const std::string &why) { mppi_destroy(h); return fail(nullptr, st, why); };
+    if (!pc_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: the producer/consumer rollout serves this shape only with s_dim = 2 a_dim, a_dim <= 4, tau <= 160 (<= 132 above 512 tiles)");
+    if (h->nbp > 1024) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: at most 1024 tiles (k = 65536) per member (the finish combines a member's records in one pass)");
+    if ((long long)h->nb * n > (1ll << 30) / 64) return refuse(MPPI_ERR_INVALID_ARG, "batched controllers: n * k too large");
+    const int B = n, s = h->s, a = h->a, HA = h->HA;
+    const size_t K = (size_t)h->K_local, rec = (size_t)h->nbp * (2 + HA), us = (size_t)HA + a;
+    auto body = [&]() -> mppi_status {
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        // the per-member buffers replace the single controller's (same names, B times the size)
+        for (float **p : {&h->d_Ubuf[0], &h->d_Ubuf[1], &h->d_cost, &h->d_part, &h->d_dbg}) { HIP_TRY(h, hipFree(*p)); *p = nullptr; }
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(h, hipMalloc((void **)&h->d_Ubuf[i], sizeof(float) * us * B));
+            HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, sizeof(float) * us * B, h->stream)); // U0 = 0, zero tails
+        }
+        HIP_TRY(h, hipMalloc((void **)&h->d_cost, sizeof(float) * K * B));
+        HIP_TRY(h, hipMemsetAsync(h->d_cost, 0, sizeof(float) * K * B, h->stream));
+        HIP_TRY(h, hipMalloc((void **)&h->d_dbg, sizeof(float) * 8 * B));
+        HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, sizeof(float) * 8 * B, h->stream));
+        // every member's record block with its neutral pads, written once (ensure_record_layout of a lone handle)
+        HIP_TRY(h, hipMalloc((void **)&h->d_part, sizeof(float) * rec * B));
+        for (int m = 0; m < B; ++m)
+            hipLaunchKernelGGL(k_fill_records, dim3((unsigned)((rec + 255) / 256)), dim3(256), 0, h->stream, h->d_part + rec * m, h->nbp, 2 + HA);
+        HIP_TRY(h, hipGetLastError());
+        h->part_nb = h->nb;
+        h->seeds.resize(B);
+        for (int m = 0; m < B; ++m) h->seeds[m] = seeds ? seeds[m] : cfg->seed + (unsigned long long)m;
+        HIP_TRY(h, hipMalloc((void **)&h->d_seeds, sizeof(unsigned long long) * B));
+        HIP_TRY(h, hipMemcpyAsync(h->d_seeds, h->seeds.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice, h->stream));
+        std::vector<float> goals((size_t)B * s);
+        for (int m = 0; m < B; ++m) for (int i = 0; i < s; ++i) goals[(size_t)m * s + i] = h->hc.goal[i];
+        HIP_TRY(h, hipMalloc((void **)&h->d_goals, sizeof(float) * goals.size()));
+        HIP_TRY(h, hipMemcpyAsync(h->d_goals, goals.data(), sizeof(float) * goals.size(), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMalloc((void **)&h->d_bx, sizeof(float) * (size_t)B * s));
+        HIP_TRY(h, hipMalloc((void **)&h->d_bu, sizeof(float) * (size_t)B * a));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return MPPI_OK;
+    };
+    h->batch = B;
+    h->fuse_step = 0; // the two launches, always
+    if (mppi_status st = body(); st != MPPI_OK) { g_create_err = h->err; mppi_destroy(h); return st; }
+    *out = h;
+    return MPPI_OK;
+}
+
+extern "C" int mppi_batch_size(const mppi_handle *h) { return h ? h->batch : 0; }
+
+#define MPPI_BATCH_ONLY(h)                                                                                          \
+    do {                                                                                                            \
+        if (!(h)) return MPPI_ERR_INVALID_ARG;                                                                      \
+        if (!(h)->batch) return fail((h), MPPI_ERR_INVALID_ARG, "not a batched handle (mppi_create_batch)");        \
+    } while (0)
+
+// rollouts of every member -> records, the finish of every member -> U', u_dev[B][a]; the sequences and the step counter advance
+static mppi_status batch_step(mppi_handle *h, hipStream_t st, const float *x_dev, float *u_dev)
+{
+    if (!pc_eligible(h)) return fail(h, MPPI_ERR_UNSUPPORTED, "batched step: the horizon exceeds what this producer count serves (tau <= 132 with 3 producers)");
+    TraceRange step_range(h, "mppi:batch_step");
+    const bool prof = h->prof_n < h->prof_cap;
+    h->kev0 = prof ? h->ev[4 * h->prof_n + 0] : nullptr; // the dispatches' own begin / end
+    h->kev1 = prof ? h->ev[4 * h->prof_n + 1] : nullptr;
+    const hipError_t e = launch_batch(h, st, x_dev);
+    h->kev0 = h->kev1 = nullptr;
+    HIP_TRY(h, e);
+    HIP_TRY(h, launch_batch_finish(h, st, u_dev, prof ? h->ev[4 * h->prof_n + 2] : nullptr, prof ? h->ev[4 * h->prof_n + 3] : nullptr));
+    if (prof) { h->prof_stream = st; h->prof_n++; }
+    h->U_advance();
+    return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_batch_set_goals(mppi_handle *h, const float *goals, int n)
+{
+    MPPI_BATCH_ONLY(h);
+    if (!goals || n != h->batch * h->s) return fail(h, MPPI_ERR_INVALID_ARG, "goals must hold n * s_dim floats");
+    MPPI_ENTER(h);
+    HIP_TRY(h, hipMemcpyAsync(h->d_goals, goals, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_batch_next(mppi_handle *h, const float *x, int n_x, float *u_out, int n_u)
+{
+    MPPI_BATCH_ONLY(h);
+    if (!x || !u_out || n_x != h->batch * h->s || n_u != h->batch * h->a) return fail(h, MPPI_ERR_INVALID_ARG, "x must hold n * s_dim floats and u_out n * a_dim");
+    MPPI_ENTER(h);
+    HIP_TRY(h, hipMemcpyAsync(h->d_bx, x, sizeof(float) * n_x, hipMemcpyHostToDevice, h->stream));
+    if (mppi_status s = batch_step(h, h->stream, h->d_bx, h->d_bu); s != MPPI_OK) return s;
+    HIP_TRY(h, hipMemcpyAsync(u_out, h->d_bu, sizeof(float) * n_u, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_batch_next_device(mppi_handle *h, const float *x_dev, float *u_dev, void *stream)
+{
+    MPPI_BATCH_ONLY(h);
+    if (!x_dev || !u_dev) return fail(h, MPPI_ERR_INVALID_ARG, "NULL device pointer");
+    MPPI_ENTER(h);
+    return batch_step(h, stream ? (hipStream_t)stream : h->stream, x_dev, u_dev);
+}
+
+extern "C" mppi_status mppi_batch_get_action_sequences(mppi_handle *h, float *U, int n)
+{
+    MPPI_BATCH_ONLY(h);
+    if (!U || n != h->batch * h->HA) return fail(h, MPPI_ERR_INVALID_ARG, "U must hold n * tau * a_dim floats");
+    MPPI_ENTER(h);
+    const size_t row = sizeof(float) * h->HA, pitch = sizeof(float) * (h->HA + h->a);
+    HIP_TRY(h, hipMemcpy2DAsync(U, row, h->U_cur(), pitch, row, h->batch, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_batch_set_action_sequences(mppi_handle *h, const float *U, int n)
+{
+    MPPI_BATCH_ONLY(h);
+    if (!U || n != h->batch * h->HA) return fail(h, MPPI_ERR_INVALID_ARG, "U must hold n * tau * a_dim floats");
+    MPPI_ENTER(h);
+    const size_t row = sizeof(float) * h->HA, pitch = sizeof(float) * (h->HA + h->a);
+    for (int i = 0; i < 2; ++i) HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, pitch * h->batch, h->stream)); // zero tails
+    h->u_cur = 0; h->u_off = 0; h->d_Uupd = nullptr;
+    HIP_TRY(h, hipMemcpy2DAsync(h->d_Ubuf[0], pitch, U, row, row, h->batch, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what, float *out, size_t n)
+{
+    MPPI_BATCH_ONLY(h);
+    if (!out) return fail(h, MPPI_ERR_INVALID_ARG, "out is NULL");
+    if (member < 0 || member >= h->batch) return fail(h, MPPI_ERR_INVALID_ARG, "member out of range");
+    MPPI_ENTER(h);
+    const size_t K = (size_t)h->K_local;
+    const float *src = nullptr;
+    size_t need = 0;
+    float *tmp = nullptr;
+    float *dbg = h->d_dbg + 8 * (size_t)member;
+    switch (what) {
+    case MPPI_DBG_COSTS: src = h->d_cost + K * member; need = K; break;
+    case MPPI_DBG_BETA: src = dbg; need = 1; break;
+    case MPPI_DBG_ETA: src = dbg + 1; need = 1; break;
+    case MPPI_DBG_AUX: src = dbg; need = 8; break;
+    case MPPI_DBG_U_UPDATED:
+        if (!h->d_Uupd) return fail(h, MPPI_ERR_INVALID_ARG, "no step has run since the action sequences were set");
+        src = h->d_Uupd + (size_t)(h->HA + h->a) * member; need = (size_t)h->HA; break;
+    case MPPI_DBG_WEIGHTS: {
+        need = K;
+        if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
+        HIP_TRY(h, hipMalloc((void **)&tmp, sizeof(float) * K));
+        hipLaunchKernelGGL(k_weights, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, (const DevConsts *)h->dC, (const float *)(h->d_cost + K * member),
+                           (int)K, (const float *)dbg, (float *)nullptr, (float *)nullptr, tmp, (const float *)nullptr);
+        src = tmp;
+        break;
+    }
+    case MPPI_DBG_NOISE: {
+        // the member's noise of the LAST step, regenerated from its Philox key at the previous step counter by the tile kernel's noise-only
+        // pass (as mppi_debug_get); the constants carry the member's key for that one launch
+        need = K * (size_t)h->HA;
+        if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
+        if (mppi_status s = ensure_eps(h); s != MPPI_OK) return s;
+        unsigned long long cur = 0;
+        HIP_TRY(h, hipMemcpyAsync(&cur, h->d_step, sizeof(cur), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (cur == 0) return fail(h, MPPI_ERR_INVALID_ARG, "no step has run yet");
+        const unsigned long long prev = cur - 1, own_seed = h->hc.seed;
+        h->hc.seed = h->seeds[member];
+        mppi_status us = upload_consts(h);
+        if (us == MPPI_OK) {
+            HIP_TRY(h, hipMemcpyAsync(h->d_step, &prev, sizeof(prev), hipMemcpyHostToDevice, h->stream));
+            const hipError_t le = launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
+            HIP_TRY(h, hipMemcpyAsync(h->d_step, &cur, sizeof(cur), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, le);
+        }
+        h->hc.seed = own_seed;
+        if (mppi_status s2 = upload_consts(h); us == MPPI_OK) us = s2;
+        if (us != MPPI_OK) return us;
+        src = h->d_eps;
+        break;
+    }
+    default: return fail(h, MPPI_ERR_INVALID_ARG, "unknown debug item");
+    }
+    if (n != need) { if (tmp) (void)hipFree(tmp); return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size"); }
+    hipError_t e = hipMemcpyAsync(out, src, sizeof(float) * need, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (tmp) (void)hipFree(tmp);
+    HIP_TRY(h, e);
     return MPPI_OK;
 }

@@ -1,6 +1,6 @@
 // mppi_handle.hip.h — host-side state of one controller (mppi_handle) and the launchers of the rollout kernels.
 // The library is several translation units compiled in parallel (mppi-tf_amd/build.py): mppi_capi.hip holds the C-ABI,
-// mppi_launch_tile.hip / _pc.hip / _mlp.hip instantiate one kernel family each for ONE action dimension per object
+// mppi_launch_tile.hip / _pc.hip / _mlp.hip / _batch.hip instantiate one kernel family each for ONE action dimension per object
 // (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels. This header is what they share.
 #pragma once
 #include "mppi_kernels.hip.h"
@@ -125,6 +125,13 @@ struct mppi_handle {
     unsigned long long pre_step = 0; // host mirror of the Philox step counter
     unsigned long long pre_count = 0; // launches since the mode was entered (parity = stream)
     unsigned next_seq() { step_seq = (step_seq + 1u) & 0x7fffffffu; if (step_seq == 0u) step_seq = 1u; return step_seq; }
+    // a batched handle (mppi_create_batch): `batch` controllers sharing this configuration, stepped together (mppi_launch_batch.hip).
+    // Per member m: x at d_bx + m*s, U in d_Ubuf[i] + m*(HA + a) (each with its zero tail), costs at d_cost + m*K, records at
+    // d_part + m*nbp*(2 + HA), beta/eta at d_dbg + 8m, Philox key d_seeds[m], goal d_goals + m*s. 0 = a plain handle.
+    int batch = 0;
+    std::vector<unsigned long long> seeds;
+    unsigned long long *d_seeds = nullptr;
+    float *d_goals = nullptr, *d_bx = nullptr, *d_bu = nullptr;
     size_t xchg_step_slots() const { return (size_t)2 * HA * shard_count * 3; }
     size_t xchg_inbox_bytes() const { return sizeof(unsigned long long) * (xchg_step_slots() + (size_t)2 * shard_count); }
 };
@@ -155,6 +162,10 @@ struct mppi_step_launch {
 };
 #define MPPI_STEP_PARAMS mppi_handle *h, hipStream_t st, const mppi_step_launch *L
 MPPI_DECL_A(mppi_launch_step_a, MPPI_STEP_PARAMS)
+// the batched step (mppi_launch_batch.hip): every member's rollout in one launch, every member's finish in another
+MPPI_DECL_A(mppi_launch_batch_a, MPPI_PC_PARAMS)
+#define MPPI_BATCH_FINISH_PARAMS mppi_handle *h, hipStream_t st, const float *U_in, float *U_out, float *u_dev, hipEvent_t ev0, hipEvent_t ev1
+MPPI_DECL_A(mppi_launch_batch_finish_a, MPPI_BATCH_FINISH_PARAMS)
 #undef MPPI_DECL_A
 // the 13-state AUV family (mppi_launch_gen.hip)
 const char *mppi_gen_fill(mppi_handle *h, const mppi_config *cfg); // NULL = ok, else why the config is invalid

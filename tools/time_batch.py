@@ -1,0 +1,95 @@
+"""Batched controllers against the alternatives a user has without them, at one shape, in one process:
+  (a) one BatchHandle of B members: one batched step = the rollout and the finish of every member, two launches;
+  (b) B plain Handles, each on its own stream, stepped round-robin from one host thread (the tools/two_controllers.py pattern);
+  (c) one plain Handle alone.
+Each figure is a host clock around `steps` pipelined next_device steps (rounds of B steps for (b)) that end in a synchronise; the three
+alternate, `reps` times, and the median is printed: us per batched step (per round for (b)), us per controller step, rollouts/s.
+    tools/time_batch.py [--steps N] [--reps R] [--quick] [--only batch|streams|single]"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import mppi_tf_amd as m  # noqa: E402
+
+GOAL = [1, 0, .5, 0, .75, 0, .25, 0]
+
+
+def kw(K, H, a):
+    return dict(k=K, tau=H, s_dim=2 * a, a_dim=a, dt=0.1, lam=1.0, sigma=0.25 * np.eye(a), goal=GOAL[:2 * a])
+
+
+def clock(enqueue, sync, steps):
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        enqueue()
+    sync()
+    return time.perf_counter() - t0
+
+
+def shape(B, K, H, a, steps, reps, only=None):
+    a_kw = kw(K, H, a)
+    hb = m.BatchHandle(n=B, **a_kw)
+    xb, ub = torch.zeros((B, 2 * a), device="cuda"), torch.zeros((B, a), device="cuda")
+    hs = [m.Handle(seed=1 + i, **a_kw) for i in range(B)]
+    xs, us = [torch.zeros(2 * a, device="cuda") for _ in hs], [torch.zeros(a, device="cuda") for _ in hs]
+    h1 = hs[0]
+
+    def sync_all():
+        torch.cuda.synchronize()
+        hb.synchronize()
+        for h in hs:
+            h.synchronize()
+
+    runs = {
+        "batch": (lambda: hb.next_device(xb.data_ptr(), ub.data_ptr(), None), hb.synchronize),
+        "streams": (lambda: [h.next_device(x.data_ptr(), u.data_ptr(), None) for h, x, u in zip(hs, xs, us)], sync_all),
+        "single": (lambda: h1.next_device(xs[0].data_ptr(), us[0].data_ptr(), None), h1.synchronize),
+    }
+    if only:  # (a kernel-trace run of one of the three: the others' kernels stay out of its statistics)
+        runs = {only: runs[only]}
+    for f, s in runs.values():  # warm-up: code objects loaded, LDS ceilings raised, clocks up
+        clock(f, s, max(50, steps // 4))
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, (f, s) in runs.items():
+            t[k].append(clock(f, s, steps) / steps)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    per = {"batch": B, "streams": B, "single": 1}
+    for k in med:
+        w = med[k]
+        print("B=%-2d K=%-5d H=%-3d a=%d  %-7s %8.2f us per %s  %7.2f us per controller step  %.3g rollouts/s" % (
+            B, K, H, a, k, w * 1e6, "batched step" if k == "batch" else ("round of %d" % B if k == "streams" else "step"),
+            w * 1e6 / per[k], per[k] * K / w), flush=True)
+    if not only:
+        print("B=%-2d K=%-5d H=%-3d a=%d  batch / streams = %.3f   (spread over %d reps: batch %.2f-%.2f us, streams %.2f-%.2f us)" % (
+            B, K, H, a, med["batch"] / med["streams"], reps, min(t["batch"]) * 1e6, max(t["batch"]) * 1e6,
+            min(t["streams"]) * 1e6, max(t["streams"]) * 1e6), flush=True)
+    hb.close()
+    for h in hs:
+        h.close()
+    return med
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--quick", action="store_true", help="one shape only: B = 4, K = 4096, H = 64, a = 2")
+    ap.add_argument("--only", choices=("batch", "streams", "single"), help="time one of the three alone")
+    o = ap.parse_args()
+    print("tools/time_batch.py: %s, %s, steps %d, reps %d" % (torch.cuda.get_device_name(0), m.__name__, o.steps, o.reps), flush=True)
+    shapes = ([(B, 4096, 64, 2) for B in (1, 2, 4, 8, 16)] + [(B, 3000, 50, 2) for B in (1, 2, 4, 8, 16)]
+              + [(B, 65536, 64, 3) for B in (1, 2, 4)])
+    if o.quick:
+        shapes = [(4, 4096, 64, 2)]
+    for B, K, H, a in shapes:
+        shape(B, K, H, a, o.steps, o.reps, o.only)
+
+
+if __name__ == "__main__":
+    main()

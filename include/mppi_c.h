@@ -407,11 +407,16 @@ mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf, size_t n);
  * form, the action limits and the Philox step counter); each member has its own state, goal, action sequence (warm-started and shifted as
  * a lone handle's) and Philox key. Member m is bit for bit the handle mppi_create makes from the same config with cfg.seed = seeds[m], fed
  * the same x, goal and sequence on the same step counter: sample costs, U' and u. Members never interact.
- * Serves the point-mass model (a_dim 1..4) with the quadratic state cost (diagonal or dense Q), either action-cost form, diagonal or dense
- * sigma, action limits, every horizon the producer/consumer rollout takes (tau <= 160; <= 132 above 512 tiles), k <= 65536 per member.
- * Refused with MPPI_ERR_UNSUPPORTED: the MLP / AUV / NNAUV / NNAUVSpeed models, the ellipse costs and StaticQuatCost, normalize_cost,
- * MPPI_FLAG_FP_CONTRACT, MPPI_FLAG_MLP_BF16X3, shard_count > 1; on the handle the tunings MPPI_TUNE_FUSED_STEP != 0, _ARMED_US,
- * _PRELAUNCH and _FORCE_TILE_KERNEL, the sequence filter and the transition log. The per-member entry points (mppi_next,
+ * Serves
+ *   - the point-mass model (a_dim 1..4) with the quadratic state cost (diagonal or dense Q), every horizon the producer/consumer rollout
+ *     takes (tau <= 160; <= 132 above 512 tiles);
+ *   - the Fossen AUV model (MPPI_MODEL_AUV with cfg.auv; s_dim 13, a_dim 6) with the quadratic state cost (diagonal or dense Q),
+ *     MPPI_STATE_COST_QUAT (StaticQuatCost) or MPPI_STATE_COST_ELLIPSE3D (ElipseCost3D), every horizon; goals are then [B, 13];
+ * each with either action-cost form, diagonal or dense sigma, action limits, k <= 65536 per member.
+ * Refused with MPPI_ERR_UNSUPPORTED: the MLP / NNAUV / NNAUVSpeed models, MPPI_MODEL_AUV without cfg.auv, the 2D ellipse cost (ElipseCost),
+ * StaticQuatCost and ElipseCost3D without the Fossen AUV model, normalize_cost, MPPI_FLAG_FP_CONTRACT, MPPI_FLAG_MLP_BF16X3,
+ * shard_count > 1; on the handle the tunings MPPI_TUNE_FUSED_STEP != 0, _ARMED_US, _PRELAUNCH and _FORCE_TILE_KERNEL (and on an AUV
+ * batch _GEN_ONE_WAVE != 0 and _MLP32_VALU != 0), the sequence filter and the transition log. The per-member entry points (mppi_next,
  * mppi_next_with_noise, mppi_next_device, mppi_set_goal, mppi_get/set_action_sequence, mppi_debug_get, mppi_shard_*, the log and CSV
  * calls) refuse a batched handle with MPPI_ERR_UNSUPPORTED; mppi_destroy, mppi_synchronize, mppi_set_action_limits,
  * mppi_get/set_step_counter, mppi_profile_begin/end and mppi_rollout_kernel_name serve it as they serve a plain one. Sizes that do not

@@ -197,6 +197,44 @@ def _mlp_desc(mlp, n_in, n_out):
     return desc, held + [desc, widths, Wp, bp]
 
 
+def _fill_13state(cfg, keep, auv, quat_cost, ellipse3d, Q):
+    """the Fossen AUV model (auv: the reference's AUVModel `parameters` dict), StaticQuatCost (quat_cost, with Q [10,10] or its 10 diagonal
+    entries) and ElipseCost3D (ellipse3d dict) into cfg, as Handle and BatchHandle take them; the arrays cfg points to are appended to
+    `keep`. Returns the Q that is left for the quadratic cost (None once StaticQuatCost took it)."""
+    if auv is not None:
+        d = AuvDesc()
+        d.mass, d.volume, d.density, d.gravity = auv["mass"], auv["volume"], auv["density"], auv.get("gravity", 0.0)
+        d.rk = int(auv.get("rk", 1))  # auv_model.py:111-114: rk defaults to 1 when the parameters do not carry it
+        for i in range(3):
+            d.cog[i], d.cob[i] = auv["cog"][i], auv["cob"][i]
+        for i, key in enumerate(("ixx", "iyy", "izz", "ixy", "ixz", "iyz")):
+            d.inertial[i] = auv["inertial"][key]
+
+        def mat6(key):  # a 6-vector is the diagonal (auv_model.py:186-195)
+            if auv.get(key) is None:
+                return None
+            m6 = np.asarray(auv[key], np.float32)
+            keep.append(f32(np.diag(m6) if m6.shape == (6,) else m6, (36,)))
+            return fp(keep[-1])
+        d.added_mass, d.linear_damping = mat6("Ma"), mat6("linear_damping")
+        d.linear_damping_forward_speed = mat6("linear_damping_forward_speed")
+        if auv.get("quad_damping") is not None:
+            keep.append(f32(auv["quad_damping"], (6,)))
+            d.quad_damping = fp(keep[-1])
+        keep.append(d)
+        cfg.model_kind, cfg.auv = MODEL_AUV, C.pointer(d)
+    if quat_cost:
+        q = f32(Q if Q is not None else np.ones(10))
+        keep.append(f32(np.diag(q) if q.ndim == 1 else q, (100,)))
+        cfg.state_cost_kind, cfg.quat_Q = STATE_COST_QUAT, fp(keep[-1])
+        Q = None
+    if ellipse3d is not None:
+        e = ellipse3d
+        keep.append(f32(list(np.ravel(e["normal"])) + list(np.ravel(e["aVec"])) + list(np.ravel(e["axis"])) + [e["speed"], e["m_state"], e["m_vel"]], (11,)))
+        cfg.state_cost_kind, cfg.ellipse3d = STATE_COST_ELLIPSE3D, fp(keep[-1])
+    return Q
+
+
 class Handle:
     """RAII wrapper of one mppi_handle (one controller on one GPU)."""
 
@@ -227,37 +265,7 @@ class Handle:
             e = [ellipse[k] for k in ("a", "b", "cx", "cy", "speed", "m_state", "m_vel")] if isinstance(ellipse, dict) else ellipse
             keep.append(f32(e, (7,)))
             cfg.state_cost_kind, cfg.ellipse = 1, fp(keep[-1])
-        if auv is not None:
-            d = AuvDesc()
-            d.mass, d.volume, d.density, d.gravity = auv["mass"], auv["volume"], auv["density"], auv.get("gravity", 0.0)
-            d.rk = int(auv.get("rk", 1))  # auv_model.py:111-114: rk defaults to 1 when the parameters do not carry it
-            for i in range(3):
-                d.cog[i], d.cob[i] = auv["cog"][i], auv["cob"][i]
-            for i, key in enumerate(("ixx", "iyy", "izz", "ixy", "ixz", "iyz")):
-                d.inertial[i] = auv["inertial"][key]
-
-            def mat6(key):  # a 6-vector is the diagonal (auv_model.py:186-195)
-                if auv.get(key) is None:
-                    return None
-                m6 = np.asarray(auv[key], np.float32)
-                keep.append(f32(np.diag(m6) if m6.shape == (6,) else m6, (36,)))
-                return fp(keep[-1])
-            d.added_mass, d.linear_damping = mat6("Ma"), mat6("linear_damping")
-            d.linear_damping_forward_speed = mat6("linear_damping_forward_speed")
-            if auv.get("quad_damping") is not None:
-                keep.append(f32(auv["quad_damping"], (6,)))
-                d.quad_damping = fp(keep[-1])
-            keep.append(d)
-            cfg.model_kind, cfg.auv = MODEL_AUV, C.pointer(d)
-        if quat_cost:
-            q = f32(Q if Q is not None else np.ones(10))
-            keep.append(f32(np.diag(q) if q.ndim == 1 else q, (100,)))
-            cfg.state_cost_kind, cfg.quat_Q = STATE_COST_QUAT, fp(keep[-1])
-            Q = None
-        if ellipse3d is not None:
-            e = ellipse3d
-            keep.append(f32(list(np.ravel(e["normal"])) + list(np.ravel(e["aVec"])) + list(np.ravel(e["axis"])) + [e["speed"], e["m_state"], e["m_vel"]], (11,)))
-            cfg.state_cost_kind, cfg.ellipse3d = STATE_COST_ELLIPSE3D, fp(keep[-1])
+        Q = _fill_13state(cfg, keep, auv, quat_cost, ellipse3d, Q)
         if nnauv is not None:
             mlp = nnauv
         if nnauv_speed is not None:
@@ -571,9 +579,12 @@ class BatchHandle:
     same two launches. Member m is bit for bit Handle(..., seed=seeds[m]) fed the same x, goal and sequence (include/mppi_c.h)."""
 
     def __init__(self, n, k, tau, s_dim, a_dim, dt=0.1, mass=1.0, lam=1.0, gamma=1.0, upsilon=1.0, sigma=None, goal=None, goals=None,
-                 Q=None, q_is_full=None, action_cost=ACTION_COST_CPP, seed=1, seeds=None, device=0, upsilon_scales_noise=False, tuning=None):
+                 Q=None, q_is_full=None, action_cost=ACTION_COST_CPP, seed=1, seeds=None, device=0, upsilon_scales_noise=False, tuning=None,
+                 auv=None, quat_cost=False, ellipse3d=None):
         """n members; seeds: n Philox keys (None: seed + m); goal: every member's goal, goals: [n, s_dim] per member (after goal);
-        the other keywords as Handle's. tuning: dict of diagnostic switches (keys of TUNING) that a batch takes."""
+        the other keywords as Handle's. tuning: dict of diagnostic switches (keys of TUNING) that a batch takes.
+        auv, quat_cost, ellipse3d: as Handle's (the Fossen AUV model, s_dim 13, a_dim 6; StaticQuatCost; ElipseCost3D); goals is then
+        [n, 13], next / next_device take x [n, 13] and give u [n, 6]."""
         lib = self.lib = load()
         self.h = _H()
         cfg = Config()
@@ -581,6 +592,7 @@ class BatchHandle:
         cfg.lam, cfg.gamma, cfg.upsilon, cfg.action_cost_kind = lam, gamma, upsilon, action_cost
         cfg.seed, cfg.device, cfg.flags = seed, device, (1 if upsilon_scales_noise else 0)
         keep = []
+        Q = _fill_13state(cfg, keep, auv, quat_cost, ellipse3d, Q)
         if sigma is not None:
             keep.append(f32(sigma, (a_dim, a_dim)))
             cfg.sigma = fp(keep[-1])

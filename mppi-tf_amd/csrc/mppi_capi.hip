@@ -838,7 +838,8 @@ extern "C" mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf,
 {
     if (!h || !buf || n == 0) return MPPI_ERR_INVALID_ARG;
     const int NG = (h->H + 3) / 4;
-    if (h->batch) std::snprintf(buf, n, "mppi::k_rollout_pc_batch<%d, %d, %d, %s, %d>", h->a, h->pc_np,
+    if (h->batch && h->is_gen) std::snprintf(buf, n, "mppi::k_rollout_auv_pc_batch<%s>", h->sigma_diag ? "true" : "false");
+    else if (h->batch) std::snprintf(buf, n, "mppi::k_rollout_pc_batch<%d, %d, %d, %s, %d>", h->a, h->pc_np,
                                 h->pc_np == 3 ? (NG <= 18 ? 6 : 11) : (NG <= 20 ? 4 : 8), h->sigma_diag ? "true" : "false", h->hc.q_full ? 2 : 0);
     else if (h->is_gen) std::snprintf(buf, n, "%s", mppi_gen_kernel_name(h));
     else if (h->hc.model_kind == MPPI_MODEL_MLP)
@@ -1542,7 +1543,9 @@ extern "C" mppi_status mppi_set_tuning(mppi_handle *h, int what, int value)
         const char *why = (what == MPPI_TUNE_FUSED_STEP && value != 0) ? "fused_step"
                         : (what == MPPI_TUNE_ARMED_US && value != 0) ? "armed_us"
                         : (what == MPPI_TUNE_PRELAUNCH && value != 0) ? "prelaunch"
-                        : (what == MPPI_TUNE_FORCE_TILE_KERNEL && value != 0) ? "force_tile_kernel" : nullptr;
+                        : (what == MPPI_TUNE_FORCE_TILE_KERNEL && value != 0) ? "force_tile_kernel"
+                        : (h->is_gen && what == MPPI_TUNE_GEN_ONE_WAVE && value != 0) ? "gen_one_wave"
+                        : (h->is_gen && what == MPPI_TUNE_MLP32_VALU && value != 0) ? "mlp32_valu" : nullptr;
         if (why) return fail(h, MPPI_ERR_UNSUPPORTED, std::string("tuning ") + why + ": a batched handle always runs the two-launch batched step");
     }
     switch (what) {
@@ -1920,13 +1923,14 @@ extern "C" mppi_status mppi_shift(const float *U, int tau, int a, const float *i
     return MPPI_OK;
 }
 
-// ---- batched controllers (mppi_create_batch; kernels in mppi_launch_batch.hip) ----------------------------------------------------
+// ---- batched controllers (mppi_create_batch; kernels in mppi_launch_batch.hip and mppi_launch_batch_gen.hip) -----------------------
 // B members share one mppi_config; each has its own x, goal, sequence and Philox key. Member m is bit for bit the lone handle made from the
 // same config with cfg.seed = seeds[m], fed the same x, goal and sequence, on the same step counter: the batched rollout is the text of
-// k_rollout_pc with per-member operands, with the instance (producers, slots) that handle would launch, and the batched finish is
-// k_finish_cols' column_combine on the member's records over the same padded record count.
+// k_rollout_pc (the point mass) or k_rollout_auv_pc (the Fossen AUV model) with per-member operands, with the instance that handle would
+// launch, and the batched finish is k_finish_cols' column_combine on the member's records over the same padded record count.
 static hipError_t launch_batch(mppi_handle *h, hipStream_t st, const float *x_dev)
 {
+    if (h->is_gen) return mppi_launch_batch_auv(h, st, x_dev);
     switch (h->a) {
     case 1: return mppi_launch_batch_a1(h, st, x_dev);
     case 2: return mppi_launch_batch_a2(h, st, x_dev);
@@ -1938,6 +1942,7 @@ static hipError_t launch_batch(mppi_handle *h, hipStream_t st, const float *x_de
 
 static hipError_t launch_batch_finish(mppi_handle *h, hipStream_t st, float *u_dev, hipEvent_t ev0, hipEvent_t ev1)
 {
+    if (h->is_gen) return mppi_launch_batch_finish_auv(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
     switch (h->a) {
     case 1: return mppi_launch_batch_finish_a1(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
     case 2: return mppi_launch_batch_finish_a2(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
@@ -1947,22 +1952,35 @@ static hipError_t launch_batch_finish(mppi_handle *h, hipStream_t st, float *u_d
     return hipErrorInvalidValue;
 }
 
+// the Fossen AUV model on its two-wave rollout (k_rollout_auv_pc, every horizon) with the step's one pass: what k_rollout_auv_pc_batch runs
+static bool auv_batch_eligible(const mppi_handle *h)
+{
+    return h->is_gen && h->hc.model_kind == MPPI_MODEL_AUV && !h->gen_one_wave && !h->normalize && h->shard_count == 1;
+}
+
 // why cfg cannot be batched (NULL: it can, as far as the config alone tells)
 static const char *batch_refusal(const mppi_config *cfg)
 {
+    const bool auv = cfg->model_kind == MPPI_MODEL_AUV;
     switch (cfg->model_kind) {
     case MPPI_MODEL_POINT_MASS: break;
-    case MPPI_MODEL_MLP: return "batched controllers: model MLP is not supported (the point-mass model only)";
-    case MPPI_MODEL_AUV: return "batched controllers: model AUV is not supported (the point-mass model only)";
-    case MPPI_MODEL_NN_AUV: return "batched controllers: model NNAUV is not supported (the point-mass model only)";
-    case MPPI_MODEL_NN_AUV_SPEED: return "batched controllers: model NNAUVSpeed is not supported (the point-mass model only)";
+    case MPPI_MODEL_MLP: return "batched controllers: model MLP is not supported (the point-mass and Fossen AUV models only)";
+    case MPPI_MODEL_AUV:
+        if (!cfg->auv) return "batched controllers: model AUV needs its mppi_auv_desc (cfg.auv)";
+        break;
+    case MPPI_MODEL_NN_AUV: return "batched controllers: model NNAUV is not supported (the point-mass and Fossen AUV models only)";
+    case MPPI_MODEL_NN_AUV_SPEED: return "batched controllers: model NNAUVSpeed is not supported (the point-mass and Fossen AUV models only)";
     default: break; // (mppi_create reports it)
     }
     switch (cfg->state_cost_kind) {
     case MPPI_STATE_COST_QUADRATIC: break;
-    case MPPI_STATE_COST_ELLIPSE: return "batched controllers: the ellipse cost (ElipseCost) is not supported (the quadratic cost only)";
-    case MPPI_STATE_COST_ELLIPSE3D: return "batched controllers: the ellipse cost (ElipseCost3D) is not supported (the quadratic cost only)";
-    case MPPI_STATE_COST_QUAT: return "batched controllers: StaticQuatCost is not supported (the quadratic cost only)";
+    case MPPI_STATE_COST_ELLIPSE: return "batched controllers: the ellipse cost (ElipseCost) is not supported (the quadratic cost, and StaticQuatCost / ElipseCost3D with the Fossen AUV model)";
+    case MPPI_STATE_COST_ELLIPSE3D:
+        if (!auv) return "batched controllers: the ellipse cost (ElipseCost3D) is served with the Fossen AUV model only";
+        break;
+    case MPPI_STATE_COST_QUAT:
+        if (!auv) return "batched controllers: StaticQuatCost is served with the Fossen AUV model only";
+        break;
     default: break;
     }
     if (cfg->normalize_cost) return "batched controllers: normalize_cost is not supported";
@@ -1982,7 +2000,8 @@ extern "C" mppi_status mppi_create_batch(const mppi_config *cfg, int n, const ui
     mppi_handle *h = nullptr;
     if (mppi_status st = mppi_create(cfg, &h); st != MPPI_OK) return st;
     auto refuse = [&](mppi_status st, const std::string &why) { mppi_destroy(h); return fail(nullptr, st, why); };
-    if (!pc_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: the producer/consumer rollout serves this shape only with s_dim = 2 a_dim, a_dim <= 4, tau <= 160 (<= 132 above 512 tiles)");
+    if (!h->is_gen && !pc_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: the producer/consumer rollout serves this shape only with s_dim = 2 a_dim, a_dim <= 4, tau <= 160 (<= 132 above 512 tiles)");
+    if (h->is_gen && !auv_batch_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: the Fossen AUV model is batched on its two-wave rollout (k_rollout_auv_pc) only");
     if (h->nbp > 1024) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: at most 1024 tiles (k = 65536) per member (the finish combines a member's records in one pass)");
     if ((long long)h->nb * n > (1ll << 30) / 64) return refuse(MPPI_ERR_INVALID_ARG, "batched controllers: n * k too large");
     const int B = n, s = h->s, a = h->a, HA = h->HA;
@@ -2037,7 +2056,9 @@ extern "C" int mppi_batch_size(const mppi_handle *h) { return h ? h->batch : 0; 
 // rollouts of every member -> records, the finish of every member -> U', u_dev[B][a]; the sequences and the step counter advance
 static mppi_status batch_step(mppi_handle *h, hipStream_t st, const float *x_dev, float *u_dev)
 {
-    if (!pc_eligible(h)) return fail(h, MPPI_ERR_UNSUPPORTED, "batched step: the horizon exceeds what this producer count serves (tau <= 132 with 3 producers)");
+    if (h->is_gen ? !auv_batch_eligible(h) : !pc_eligible(h))
+        return fail(h, MPPI_ERR_UNSUPPORTED, h->is_gen ? "batched step: the Fossen AUV model runs on k_rollout_auv_pc only"
+                                                       : "batched step: the horizon exceeds what this producer count serves (tau <= 132 with 3 producers)");
     TraceRange step_range(h, "mppi:batch_step");
     const bool prof = h->prof_n < h->prof_cap;
     h->kev0 = prof ? h->ev[4 * h->prof_n + 0] : nullptr; // the dispatches' own begin / end
@@ -2134,8 +2155,8 @@ extern "C" mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what
         break;
     }
     case MPPI_DBG_NOISE: {
-        // the member's noise of the LAST step, regenerated from its Philox key at the previous step counter by the tile kernel's noise-only
-        // pass (as mppi_debug_get); the constants carry the member's key for that one launch
+        // the member's noise of the LAST step, regenerated from its Philox key at the previous step counter by the noise-only pass of the
+        // tile kernel (the point mass) or of k_rollout_gen (the AUV), as mppi_debug_get; the constants carry the member's key for that launch
         need = K * (size_t)h->HA;
         if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
         if (mppi_status s = ensure_eps(h); s != MPPI_OK) return s;
@@ -2148,7 +2169,8 @@ extern "C" mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what
         mppi_status us = upload_consts(h);
         if (us == MPPI_OK) {
             HIP_TRY(h, hipMemcpyAsync(h->d_step, &prev, sizeof(prev), hipMemcpyHostToDevice, h->stream));
-            const hipError_t le = launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
+            const hipError_t le = h->is_gen ? mppi_launch_gen(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps)
+                                            : launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
             HIP_TRY(h, hipMemcpyAsync(h->d_step, &cur, sizeof(cur), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, le);
         }

@@ -1,7 +1,8 @@
 // mppi_handle.hip.h — host-side state of one controller (mppi_handle) and the launchers of the rollout kernels.
 // The library is several translation units compiled in parallel (mppi-tf_amd/build.py): mppi_capi.hip holds the C-ABI,
 // mppi_launch_tile.hip / _pc.hip / _mlp.hip / _batch.hip instantiate one kernel family each for ONE action dimension per object
-// (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels. This header is what they share.
+// (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step. This header is
+// what they share.
 #pragma once
 #include "mppi_kernels.hip.h"
 #include <hip/hip_ext.h>
@@ -125,7 +126,8 @@ struct mppi_handle {
     unsigned long long pre_step = 0; // host mirror of the Philox step counter
     unsigned long long pre_count = 0; // launches since the mode was entered (parity = stream)
     unsigned next_seq() { step_seq = (step_seq + 1u) & 0x7fffffffu; if (step_seq == 0u) step_seq = 1u; return step_seq; }
-    // a batched handle (mppi_create_batch): `batch` controllers sharing this configuration, stepped together (mppi_launch_batch.hip).
+    // a batched handle (mppi_create_batch): `batch` controllers sharing this configuration, stepped together (mppi_launch_batch.hip; the
+    // Fossen AUV model: mppi_launch_batch_gen.hip).
     // Per member m: x at d_bx + m*s, U in d_Ubuf[i] + m*(HA + a) (each with its zero tail), costs at d_cost + m*K, records at
     // d_part + m*nbp*(2 + HA), beta/eta at d_dbg + 8m, Philox key d_seeds[m], goal d_goals + m*s. 0 = a plain handle.
     int batch = 0;
@@ -178,5 +180,10 @@ hipError_t mppi_gen_model_step(mppi_handle *h, hipStream_t st, const float *x, i
 hipError_t mppi_gen_costs(mppi_handle *h, hipStream_t st, const float *x, const float *u, const float *eps, int k, float *os, float *oa, float *ot);
 hipError_t mppi_gen_auv_pieces(mppi_handle *h, hipStream_t st, const float *x, const float *u, int k, float *out);
 hipError_t mppi_gen_e3_terms(mppi_handle *h, hipStream_t st, const float *x, int k, int in_plane, float *out);
+const void *mppi_gen_dev_consts(const mppi_handle *h); // the handle's GenConsts on the device
+// the batched step of the Fossen AUV model (mppi_launch_batch_gen.hip): every member's rollout in one launch (k_rollout_auv_pc_batch),
+// every member's finish in another (k_finish_cols_batch<6>)
+hipError_t mppi_launch_batch_auv(MPPI_PC_PARAMS);
+hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS);
 #define MPPI_CAT_(a, b) a##b
 #define MPPI_CAT(a, b) MPPI_CAT_(a, b)

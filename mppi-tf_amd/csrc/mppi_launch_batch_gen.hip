@@ -1,0 +1,33 @@
+// mppi_launch_batch_gen.hip — instantiates the batched step of the Fossen AUV model: k_rollout_auv_pc_batch (mppi_gen.hip.h) and
+// k_finish_cols_batch<6> (mppi_kernels.hip.h). B AUV controllers that share one configuration step in the same two launches as one
+// controller. A unit of its own: the gen unit's object stays as it was, and the longest compile of the parallel build stays where it is.
+#define MPPI_UNIT_BATCH_GEN // (mppi_gen.hip.h: its non-template kernels live in the gen unit)
+#include "mppi_handle.hip.h"
+#include "mppi_gen.hip.h"
+
+// Every member's rollouts: one flat grid of B * W workgroups, W = (nb + 1) / 2 per member (two tiles per workgroup), as mppi_launch_gen's
+// k_rollout_auv_pc launch per member. The SIMD-true roles are enabled by the TOTAL workgroup count, as the lone launcher decides them.
+hipError_t mppi_launch_batch_auv(MPPI_PC_PARAMS)
+{
+    const int W = (h->nb + 1) / 2;
+    const int wgs = W * h->batch;
+    const int balance = (wgs <= 2 * h->n_cu && !h->pc_no_balance) ? 1 : 0;
+    const PcBatchArgs bt{h->d_seeds, h->d_goals, h->nb, h->HA + h->a, h->nbp * (2 + h->HA)};
+    const GenConsts *G = static_cast<const GenConsts *>(mppi_gen_dev_consts(h));
+    if (h->sigma_diag)
+        hipExtLaunchKernelGGL(k_rollout_auv_pc_batch<true>, dim3(wgs), dim3(kAuvPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, G,
+                              x_dev, h->U_cur(), (const unsigned long long *)h->d_step, h->d_cost, h->d_part, 1, h->nbp, h->nb, balance, bt);
+    else
+        hipExtLaunchKernelGGL(k_rollout_auv_pc_batch<false>, dim3(wgs), dim3(kAuvPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, G,
+                              x_dev, h->U_cur(), (const unsigned long long *)h->d_step, h->d_cost, h->d_part, 1, h->nbp, h->nb, balance, bt);
+    return hipGetLastError();
+}
+
+// the finish of every member: one workgroup per (member, column); reads U_in, writes U_out and u_dev [B][6]
+hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS)
+{
+    hipExtLaunchKernelGGL(k_finish_cols_batch<kGenA>, dim3(h->HA * h->batch), dim3(kThreads), 0, st, ev0, ev1, 0, (const float *)h->d_part, h->nbp,
+                          h->nbp, h->HA, h->nbp * (2 + h->HA), h->hc.neg_inv_lambda, U_in, U_out, h->HA + h->a, u_dev, h->d_step, h->d_dbg,
+                          (const float *)h->d_clip);
+    return hipGetLastError();
+}

@@ -140,6 +140,8 @@ hipError_t mppi_gen_upload(mppi_handle *h)
     return hipStreamSynchronize(h->stream);
 }
 
+const void *mppi_gen_dev_consts(const mppi_handle *h) { return gs(h)->dG; }
+
 void mppi_gen_destroy(mppi_handle *h)
 {
     GenState *g = gs(h);

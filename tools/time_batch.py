@@ -4,7 +4,9 @@
   (c) one plain Handle alone.
 Each figure is a host clock around `steps` pipelined next_device steps (rounds of B steps for (b)) that end in a synchronise; the three
 alternate, `reps` times, and the median is printed: us per batched step (per round for (b)), us per controller step, rollouts/s.
-    tools/time_batch.py [--steps N] [--reps R] [--quick] [--only batch|streams|single]"""
+--model auv: the Fossen AUV model at the reference's task (mppi_tf_amd.auv.auv_task: rexrov2, rk2, Sigma = 1500 I, the static goal),
+with the x0 of that task for every controller.
+    tools/time_batch.py [--model pm|auv] [--steps N] [--reps R] [--quick] [--only batch|streams|single] [--shape B,K,H] [--dry-run]"""
 import argparse
 import os
 import sys
@@ -23,6 +25,20 @@ def kw(K, H, a):
     return dict(k=K, tau=H, s_dim=2 * a, a_dim=a, dt=0.1, lam=1.0, sigma=0.25 * np.eye(a), goal=GOAL[:2 * a])
 
 
+def auv_kw(K, H):
+    """the reference's AUV task as Handle / BatchHandle keywords (seed and x0 dropped: the caller gives the seeds, x0 is the state)"""
+    from mppi_tf_amd.auv import auv_task
+    t = auv_task(H)
+    return {k: v for k, v in t.items() if k not in ("seed", "x0")} | dict(k=K), np.asarray(t["x0"], np.float32)
+
+
+def configs(model, K, H, a):
+    """-> (keywords of Handle / BatchHandle, x0 of one controller)"""
+    if model == "auv":
+        return auv_kw(K, H)
+    return kw(K, H, a), np.zeros(2 * a, np.float32)
+
+
 def clock(enqueue, sync, steps):
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -31,12 +47,14 @@ def clock(enqueue, sync, steps):
     return time.perf_counter() - t0
 
 
-def shape(B, K, H, a, steps, reps, only=None):
-    a_kw = kw(K, H, a)
+def shape(B, K, H, a, steps, reps, only=None, model="pm"):
+    a_kw, x0 = configs(model, K, H, a)
+    a, s = a_kw["a_dim"], a_kw["s_dim"]
     hb = m.BatchHandle(n=B, **a_kw)
-    xb, ub = torch.zeros((B, 2 * a), device="cuda"), torch.zeros((B, a), device="cuda")
+    xb, ub = torch.from_numpy(np.tile(x0, (B, 1))).cuda(), torch.zeros((B, a), device="cuda")
     hs = [m.Handle(seed=1 + i, **a_kw) for i in range(B)]
-    xs, us = [torch.zeros(2 * a, device="cuda") for _ in hs], [torch.zeros(a, device="cuda") for _ in hs]
+    xs, us = [torch.from_numpy(x0.copy()).cuda() for _ in hs], [torch.zeros(a, device="cuda") for _ in hs]
+    assert xb.shape == (B, s)
     h1 = hs[0]
 
     def sync_all():
@@ -81,14 +99,32 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--quick", action="store_true", help="one shape only: B = 4, K = 4096, H = 64, a = 2")
     ap.add_argument("--only", choices=("batch", "streams", "single"), help="time one of the three alone")
+    ap.add_argument("--model", choices=("pm", "auv"), default="pm", help="pm: the point mass; auv: the Fossen AUV at the reference's task")
+    ap.add_argument("--shape", help="one shape only: B,K,H (the action dimension: 2 for pm, 6 for auv)")
+    ap.add_argument("--dry-run", action="store_true", help="print the shapes and build their configurations, time nothing (no GPU)")
     o = ap.parse_args()
-    print("tools/time_batch.py: %s, %s, steps %d, reps %d" % (torch.cuda.get_device_name(0), m.__name__, o.steps, o.reps), flush=True)
-    shapes = ([(B, 4096, 64, 2) for B in (1, 2, 4, 8, 16)] + [(B, 3000, 50, 2) for B in (1, 2, 4, 8, 16)]
-              + [(B, 65536, 64, 3) for B in (1, 2, 4)])
+    if o.model == "auv":
+        shapes = ([(B, 4096, 40, 6) for B in (1, 2, 4, 8, 16)] + [(B, 16384, 40, 6) for B in (1, 2, 4, 8, 16)]
+                  + [(B, 65536, 64, 6) for B in (1, 2)])
+        quick = (16, 4096, 40, 6)
+    else:
+        shapes = ([(B, 4096, 64, 2) for B in (1, 2, 4, 8, 16)] + [(B, 3000, 50, 2) for B in (1, 2, 4, 8, 16)]
+                  + [(B, 65536, 64, 3) for B in (1, 2, 4)])
+        quick = (4, 4096, 64, 2)
     if o.quick:
-        shapes = [(4, 4096, 64, 2)]
+        shapes = [quick]
+    if o.shape:
+        B, K, H = (int(v) for v in o.shape.split(","))
+        shapes = [(B, K, H, 6 if o.model == "auv" else 2)]
+    if o.dry_run:
+        for B, K, H, a in shapes:
+            c, x0 = configs(o.model, K, H, a)
+            print("B=%-2d K=%-5d H=%-3d a=%d  %s" % (B, K, H, c["a_dim"], sorted(c)), flush=True)
+        return
+    print("tools/time_batch.py: %s, %s, model %s, steps %d, reps %d" % (torch.cuda.get_device_name(0), m.__name__, o.model, o.steps, o.reps),
+          flush=True)
     for B, K, H, a in shapes:
-        shape(B, K, H, a, o.steps, o.reps, o.only)
+        shape(B, K, H, a, o.steps, o.reps, o.only, o.model)
 
 
 if __name__ == "__main__":

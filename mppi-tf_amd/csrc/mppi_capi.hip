@@ -519,18 +519,27 @@ extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
 }
 
 // kernel dispatch: the rollout kernels are instantiated in their own translation units (mppi_launch_*.hip, one per
-// kernel family and action dimension, compiled in parallel); mppi_handle.hip.h declares their launchers.
+// kernel family and action dimension, compiled in parallel); mppi_handle.hip.h declares their entry points, one row per action dimension.
+#define MPPI_UNIT_ROW(N)                                                                                                  \
+    {mppi_tile_a##N, mppi_pc_a##N, mppi_mlp_a##N, mppi_step_a##N, mppi_batch_a##N, mppi_batch_finish_a##N, mppi_tile_name_a##N, \
+     mppi_pc_name_a##N, mppi_mlp_name_a##N, mppi_step_name_a##N, mppi_batch_name_a##N}
+static const mppi_unit_a kUnits[4] = {MPPI_UNIT_ROW(1), MPPI_UNIT_ROW(2), MPPI_UNIT_ROW(3), MPPI_UNIT_ROW(4)};
+#undef MPPI_UNIT_ROW
+static const mppi_unit_a *unit(const mppi_handle *h) { return h->a >= 1 && h->a <= 4 ? &kUnits[h->a - 1] : nullptr; }
+
+// the entry point `fn` of the handle's action dimension (none above 4: such a handle runs no rollout kernel)
+template <typename... P, typename... Args>
+static hipError_t per_a(mppi_handle *h, hipError_t (*mppi_unit_a::*fn)(P...), Args... args)
+{
+    const mppi_unit_a *u = unit(h);
+    return u ? (u->*fn)(h, args...) : hipErrorInvalidValue;
+}
+
 static hipError_t launch_tile(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev,
                               const float *eps, float *cost, float *part, float *noise_out)
 {
     if (!h->no_rollout.empty()) return hipErrorNotSupported;
-    switch (h->a) {
-    case 1: return mppi_launch_tile_a1(h, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
-    case 2: return mppi_launch_tile_a2(h, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
-    case 3: return mppi_launch_tile_a3(h, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
-    case 4: return mppi_launch_tile_a4(h, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
-    }
-    return hipErrorInvalidValue;
+    return per_a(h, &mppi_unit_a::tile, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
 }
 
 // the point-mass model with the quadratic (diagonal or dense Q) or the elliptic state cost; horizon groups per producer must fit the registers
@@ -538,28 +547,6 @@ static bool pc_eligible(const mppi_handle *h)
 {
     const bool cost_ok = h->hc.state_cost_kind == MPPI_STATE_COST_QUADRATIC || (h->hc.state_cost_kind == MPPI_STATE_COST_ELLIPSE && h->s >= 4 && !h->hc.q_full);
     return !h->is_gen && h->no_rollout.empty() && h->R == 64 && !h->force_tile && h->H <= (h->pc_np == 3 ? 132 : 160) && cost_ok;
-}
-
-static hipError_t launch_pc(mppi_handle *h, hipStream_t st, const float *x_dev)
-{
-    switch (h->a) {
-    case 1: return mppi_launch_pc_a1(h, st, x_dev);
-    case 2: return mppi_launch_pc_a2(h, st, x_dev);
-    case 3: return mppi_launch_pc_a3(h, st, x_dev);
-    case 4: return mppi_launch_pc_a4(h, st, x_dev);
-    }
-    return hipErrorInvalidValue;
-}
-
-static hipError_t launch_step(mppi_handle *h, hipStream_t st, const mppi_step_launch *L)
-{
-    switch (h->a) {
-    case 1: return mppi_launch_step_a1(h, st, L);
-    case 2: return mppi_launch_step_a2(h, st, L);
-    case 3: return mppi_launch_step_a3(h, st, L);
-    case 4: return mppi_launch_step_a4(h, st, L);
-    }
-    return hipErrorInvalidValue;
 }
 
 // What k_step_pc (mppi_step.hip.h) serves: the producer/consumer path's hot shape — point mass, diagonal quadratic cost, the step's
@@ -574,17 +561,22 @@ static bool fuse_ok(const mppi_handle *h) { return h->fuse_step && step_shape_ok
 // mppi_next may arm the next step (MPPI_TUNE_ARMED_US > 0, a large-BAR system)
 static bool arm_ok(const mppi_handle *h) { return h->arm_us > 0 && step_shape_ok(h) && h->d_xslot != nullptr; }
 
-static hipError_t launch_mlp(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev,
-                             const float *eps, float *cost)
+// Which kernel family serves the rollout launch a profiled step brackets (ev[0] .. ev[1], mppi_c.h): the batched rollout; the fused
+// k_step_pc (whole_step: the caller runs a complete control step, which may be one launch); k_rollout_pc (with normalizeCost its
+// weights-only second pass); the learned-model or 13-state kernels; else the tile kernel (with normalizeCost, these three run the cost-only pass).
+enum Route { ROUTE_BATCH, ROUTE_STEP, ROUTE_PC, ROUTE_TILE, ROUTE_MLP, ROUTE_GEN };
+static Route rollout_route(const mppi_handle *h, int src, const float *noise_out, bool whole_step)
 {
-    switch (h->a) {
-    case 1: return mppi_launch_mlp_a1(h, st, src, mode, x_dev, U_dev, eps, cost);
-    case 2: return mppi_launch_mlp_a2(h, st, src, mode, x_dev, U_dev, eps, cost);
-    case 3: return mppi_launch_mlp_a3(h, st, src, mode, x_dev, U_dev, eps, cost);
-    case 4: return mppi_launch_mlp_a4(h, st, src, mode, x_dev, U_dev, eps, cost);
-    }
-    return hipErrorInvalidValue;
+    const bool philox = src == SRC_PHILOX && noise_out == nullptr;
+    if (h->batch) return ROUTE_BATCH;
+    if (whole_step && philox && fuse_ok(h)) return ROUTE_STEP;
+    if (h->is_gen) return ROUTE_GEN;
+    if (h->hc.model_kind == MPPI_MODEL_MLP) return ROUTE_MLP;
+    return philox && pc_eligible(h) ? ROUTE_PC : ROUTE_TILE;
 }
+
+// the next rollout launch on this profiled step's rollout events (hipExtLaunchKernel: the dispatch's own begin / end), or on none
+static void kernel_events(mppi_handle *h, bool on) { h->kev0 = on ? h->ev[4 * h->prof_n + 0] : nullptr; h->kev1 = on ? h->ev[4 * h->prof_n + 1] : nullptr; }
 
 // Combine nb records (element (b,col) at recs[b*sb + col*sc]) and, if apply, update: U' = U_in + V/eta -> U_out,
 // u_out = U'[0]. More than 1024 records are first folded 16:1 (k_combine_group) into row-major scratch.
@@ -743,32 +735,31 @@ static hipError_t ensure_record_layout(mppi_handle *h, hipStream_t st, int n_til
 // rollouts of this shard -> partial records in d_part; *nrec = how many. Handles normalizeCost.
 static mppi_status enqueue_partials(mppi_handle *h, hipStream_t st, int src, const float *x_dev, const float *eps, float *noise_out, int *nrec)
 {
-    const bool mlp = h->hc.model_kind == MPPI_MODEL_MLP;
-    const bool gen = h->is_gen != 0;
+    const Route route = rollout_route(h, src, noise_out, false);
+    const bool mlp = route == ROUTE_MLP;
+    const bool gen = route == ROUTE_GEN;
     TraceRange tr(h, "mppi:rollout");
     *nrec = h->nbp; // every slot: those no tile owns hold neutral records
     h->norm_two_pass = 0;
     HIP_TRY(h, ensure_record_layout(h, st, (mlp && !h->normalize) ? h->nb_mlp : h->nb)); // (normalizeCost: the tile kernel writes the records)
     if (!h->normalize) {
         const bool prof = h->prof_n < h->prof_cap;
-        const bool pc = !mlp && src == SRC_PHILOX && noise_out == nullptr && pc_eligible(h);
-        const bool kernel_events = prof && (mlp || pc || gen); // the kernel's own begin/end; other kernels: events around the launch
-        if (prof && !kernel_events) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 0], st));
-        h->kev0 = kernel_events ? h->ev[4 * h->prof_n + 0] : nullptr;
-        h->kev1 = kernel_events ? h->ev[4 * h->prof_n + 1] : nullptr;
+        const bool kernel_events_on = prof && route != ROUTE_TILE; // the kernel's own begin/end; the tile kernel: events around the launch
+        if (prof && !kernel_events_on) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 0], st));
+        kernel_events(h, kernel_events_on);
         hipError_t le = gen ? mppi_launch_gen(h, st, src, MODE_ROLLOUT, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out)
-                      : mlp ? launch_mlp(h, st, src, MODE_ROLLOUT, x_dev, h->U_cur(), eps, h->d_cost)
-                      : pc  ? launch_pc(h, st, x_dev)
-                            : launch_tile(h, st, src, MODE_ROLLOUT, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out);
+                      : mlp ? per_a(h, &mppi_unit_a::mlp, st, src, MODE_ROLLOUT, x_dev, h->U_cur(), eps, h->d_cost)
+                      : route == ROUTE_PC ? per_a(h, &mppi_unit_a::pc, st, x_dev)
+                                          : launch_tile(h, st, src, MODE_ROLLOUT, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out);
         h->kev0 = h->kev1 = nullptr;
         HIP_TRY(h, le);
-        if (prof && !kernel_events) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 1], st));
+        if (prof && !kernel_events_on) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 1], st));
         return MPPI_OK;
     }
     if (h->shard_count != 1) return fail(h, MPPI_ERR_UNSUPPORTED, "normalize_cost on a sharded handle: mppi_shard_cost_range, reduce the ranges over the ranks, mppi_shard_partial_normalized");
     // Py normalizeCost (controller_base.py:468-474): costs, global min/max, then the update on
     // c' = (c-min)/(max-min) with the SAME noise (regenerated from the same Philox counters).
-    if (!mlp && !gen && src == SRC_PHILOX && noise_out == nullptr && pc_eligible(h)) {
+    if (route == ROUTE_PC) {
         // Fast form on the producer/consumer kernel: exp(-(c' - min c')/lambda) = exp(-(c - min c)/(lambda (max - min))), so the
         // normalised update is the plain one at another temperature. Pass 1 (PC_PASS_COSTS): the plain pass at lambda for the costs, every tile
         // leaving its (min, max); pass 2 (PC_PASS_WEIGHTS, r04): no rollouts — the global range from the tile pairs, the weights from the stored
@@ -777,11 +768,10 @@ static mppi_status enqueue_partials(mppi_handle *h, hipStream_t st, int src, con
         const bool prof2 = h->prof_n < h->prof_cap;
         h->kev0 = h->kev1 = nullptr;
         h->pc_pass = PC_PASS_COSTS;
-        hipError_t le = launch_pc(h, st, x_dev);
+        hipError_t le = per_a(h, &mppi_unit_a::pc, st, x_dev);
         h->pc_pass = PC_PASS_PLAIN;
         HIP_TRY(h, le);
-        h->kev0 = prof2 ? h->ev[4 * h->prof_n + 0] : nullptr; // a profiled step reports the second pass (the one whose records are used)
-        h->kev1 = prof2 ? h->ev[4 * h->prof_n + 1] : nullptr;
+        kernel_events(h, prof2); // a profiled step reports the second pass (the one whose records are used)
         // every workgroup of the second pass reduces the nb tile pairs itself: nb^2 x 8 bytes of L2 reads in all — 8 MB at 1024 tiles, too much
         // beyond a few thousand (K > 131072 on one GPU): there the range comes from ONE k_cost_minmax launch over the costs instead
         const int many_tiles = h->nb > 2048;
@@ -790,7 +780,7 @@ static mppi_status enqueue_partials(mppi_handle *h, hipStream_t st, int src, con
             HIP_TRY(h, hipGetLastError());
         }
         h->pc_pass = PC_PASS_WEIGHTS; h->pc_range_given = many_tiles;
-        le = launch_pc(h, st, x_dev);
+        le = per_a(h, &mppi_unit_a::pc, st, x_dev);
         h->pc_pass = PC_PASS_PLAIN; h->pc_range_given = 0;
         h->kev0 = h->kev1 = nullptr;
         HIP_TRY(h, le);
@@ -800,7 +790,7 @@ static mppi_status enqueue_partials(mppi_handle *h, hipStream_t st, int src, con
     const bool prof_n = h->prof_n < h->prof_cap; // a profiled step brackets the cost pass (the dominant launch) here
     if (prof_n) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 0], st));
     if (gen) HIP_TRY(h, mppi_launch_gen(h, st, src, MODE_COST_ONLY, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out));
-    else if (mlp) HIP_TRY(h, launch_mlp(h, st, src, MODE_COST_ONLY, x_dev, h->U_cur(), eps, h->d_cost));
+    else if (mlp) HIP_TRY(h, per_a(h, &mppi_unit_a::mlp, st, src, MODE_COST_ONLY, x_dev, h->U_cur(), eps, h->d_cost));
     else HIP_TRY(h, launch_tile(h, st, src, MODE_COST_ONLY, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out));
     if (prof_n) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 1], st));
     hipLaunchKernelGGL(k_cost_minmax, dim3(1), dim3(1024), 0, st, h->d_cost, h->K_local, h->d_mm, 0.0f, (float *)nullptr, (float *)nullptr);
@@ -832,36 +822,22 @@ extern "C" mppi_status mppi_synchronize(mppi_handle *h)
     return MPPI_OK;
 }
 
-// The rollout kernel instance a fused (Philox) step of this handle launches — the same decisions as enqueue_partials /
-// launch_pc / launch_tile / launch_mlp_a, spelled the way rocprofv3 prints the instance.
+// The rollout kernel instance a (Philox) step of this handle launches, as rocprofv3 prints it: the route and the family's pick, no launch.
 extern "C" mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf, size_t n)
 {
     if (!h || !buf || n == 0) return MPPI_ERR_INVALID_ARG;
-    const int NG = (h->H + 3) / 4;
-    if (h->batch && h->is_gen) std::snprintf(buf, n, "mppi::k_rollout_auv_pc_batch<%s>", h->sigma_diag ? "true" : "false");
-    else if (h->batch) std::snprintf(buf, n, "mppi::k_rollout_pc_batch<%d, %d, %d, %s, %d>", h->a, h->pc_np,
-                                h->pc_np == 3 ? (NG <= 18 ? 6 : 11) : (NG <= 20 ? 4 : 8), h->sigma_diag ? "true" : "false", h->hc.q_full ? 2 : 0);
-    else if (h->is_gen) std::snprintf(buf, n, "%s", mppi_gen_kernel_name(h));
-    else if (h->hc.model_kind == MPPI_MODEL_MLP)
-        if (h->mlp_small == 32 && h->mlp_bx3) std::snprintf(buf, n, "mppi::k_rollout_mlp32_bx3<%d>", h->a);
-        else if (h->mlp_small == 32 && h->mlp32_valu == 0) std::snprintf(buf, n, "mppi::k_rollout_mlp32_pc<%d, %s>", h->a, h->sigma_diag ? "true" : "false");
-        else if (h->mlp_small == 32 && h->mlp32_valu == 2) std::snprintf(buf, n, "mppi::k_rollout_mlp32<%d>", h->a);
-        else if (h->mlp_small) std::snprintf(buf, n, "mppi::k_rollout_mlp_small<%d, %d>", h->a, h->mlp_small);
-        else if (h->mlp_v2 && !h->mlp_bx3) std::snprintf(buf, n, "mppi::k_rollout_mlp2<%d, %s, 0>", h->a, h->sigma_diag ? "true" : "false");
-        else if (h->mlp_bx3) std::snprintf(buf, n, "mppi::k_rollout_mlp_bx3<%d, %s, 0>", h->a, h->sigma_diag ? "true" : "false");
-        else std::snprintf(buf, n, "mppi::k_rollout_mlp<%d, %s>", h->a, h->sigma_diag ? "true" : "false");
-    else if (fuse_ok(h)) // the whole step in one launch (mppi_step.hip.h)
-        if (h->fuse_step != 2 && NG <= 21) std::snprintf(buf, n, "mppi::k_step_pc<%d, 7, 3, %s, 1>", h->a, h->sigma_diag ? "true" : "false");
-        else std::snprintf(buf, n, "mppi::k_step_pc<%d, 5, %d, %s, 1>", h->a, NG <= 20 ? 4 : 8, h->sigma_diag ? "true" : "false");
-    else if (pc_eligible(h)) // (normalizeCost: two passes of it on the fused path; injected noise runs the tile kernel)
-    {
-        const int ck = h->hc.state_cost_kind == MPPI_STATE_COST_ELLIPSE ? 1 : (h->hc.q_full ? 2 : (h->fp_contract ? 3 : 0)); // PC_COST_* (spelled out as the profiler spells it)
-        // (normalizeCost: the records come from the weights-only second pass, PC_PASS_WEIGHTS = 2, whose one instance is the diagonal-Q one)
-        std::snprintf(buf, n, "mppi::k_rollout_pc<%d, %d, %d, %s, %d, %d>", h->a, h->pc_np,
-                      h->pc_np == 3 ? (NG <= 18 ? 6 : 11) : (NG <= 20 ? 4 : 8), h->sigma_diag ? "true" : "false", h->normalize ? 0 : ck, h->normalize ? 2 : 0);
+    const mppi_unit_a *u = unit(h);
+    const char *name = nullptr;
+    switch (rollout_route(h, SRC_PHILOX, nullptr, true)) {
+    case ROUTE_BATCH: name = h->is_gen ? mppi_batch_auv_name(h) : u ? u->batch_name(h) : nullptr; break;
+    case ROUTE_STEP: name = u ? u->step_name(h, STEP_FUSE) : nullptr; break;
+    case ROUTE_PC: name = u ? u->pc_name(h, h->normalize ? PC_PASS_WEIGHTS : PC_PASS_PLAIN) : nullptr; break;
+    case ROUTE_TILE: name = u ? u->tile_name(h, SRC_PHILOX, h->normalize ? MODE_COST_ONLY : MODE_ROLLOUT) : nullptr; break;
+    case ROUTE_MLP: name = u ? u->mlp_name(h, SRC_PHILOX) : nullptr; break;
+    case ROUTE_GEN: name = mppi_gen_name(h, h->normalize ? MODE_COST_ONLY : MODE_ROLLOUT); break;
     }
-    else
-        std::snprintf(buf, n, "mppi::k_rollout_tile<%d, %d, %s, 0, %d>", h->a, h->R, h->hc.q_full ? "true" : "false", h->normalize ? 2 : 0);
+    if (!name) return MPPI_ERR_UNSUPPORTED; // (no rollout kernel serves the handle)
+    std::snprintf(buf, n, "%s", name);
     return MPPI_OK;
 }
 
@@ -936,10 +912,9 @@ static mppi_status fused_step(mppi_handle *h, hipStream_t st, const float *x_dev
 {
     TraceRange tr(h, "mppi:rollout");
     const bool prof = h->prof_n < h->prof_cap;
-    h->kev0 = prof ? h->ev[4 * h->prof_n + 0] : nullptr; // the launch's own begin / end
-    h->kev1 = prof ? h->ev[4 * h->prof_n + 1] : nullptr;
+    kernel_events(h, prof); // the launch's own begin / end
     const mppi_step_launch L{STEP_FUSE, x_dev, h->U_cur(), h->U_other(), u_dev, h->next_seq()};
-    const hipError_t e = launch_step(h, st, &L);
+    const hipError_t e = per_a(h, &mppi_unit_a::step, st, &L);
     h->kev0 = h->kev1 = nullptr;
     HIP_TRY(h, e);
     if (prof) { // (no finish launch: an empty interval)
@@ -961,7 +936,7 @@ static mppi_status arm_launch(mppi_handle *h, const float *U_in, float *U_out, u
     if (!(mode & STEP_FUSE)) HIP_TRY(h, ensure_record_layout(h, h->stream, h->nb));
     const mppi_step_launch L{mode, nullptr, U_in, U_out, u_arg, seq};
     h->kev0 = h->kev1 = nullptr;
-    HIP_TRY(h, launch_step(h, h->stream, &L));
+    HIP_TRY(h, per_a(h, &mppi_unit_a::step, h->stream, &L));
     if (!(mode & STEP_FUSE)) {
         h->norm_two_pass = 0;
         HIP_TRY(h, launch_finish(h, h->stream, h->d_part, 1, h->nbp, h->nbp, U_in, U_out, u_arg, nullptr, 1, false, seq));
@@ -981,8 +956,7 @@ static mppi_status arm_launch(mppi_handle *h, const float *U_in, float *U_out, u
 // (one round of the grid: a rollout with workgroups still undispatched while the NEXT step's waiting workgroups hold the slots would never finish)
 static int pre_slots(const mppi_handle *h)
 {
-    const int NG = (h->H + 3) / 4;
-    const int per_cu = h->pc_np == 3 ? (NG <= 18 && 6 * 4 * h->a <= 80 ? 4 : 2) : 3; // k_step_pc's __launch_bounds__
+    const int per_cu = h->pc_np == 3 ? (mppi_pc_slots(3, h->H) == 6 && 6 * 4 * h->a <= 80 ? 4 : 2) : 3; // k_step_pc's __launch_bounds__
     return per_cu * h->n_cu;
 }
 static bool pre_shape_ok(const mppi_handle *h) { return step_shape_ok(h) && (fuse_ok(h) || (h->nb > 128 && h->nb <= pre_slots(h))) && h->d_arm != nullptr; }
@@ -1028,11 +1002,10 @@ static mppi_status pre_step(mppi_handle *h, const float *x_dev, float *u_dev)
     {
         TraceRange tr(h, "mppi:rollout");
         const bool prof = h->prof_n < h->prof_cap;
-        h->kev0 = prof ? h->ev[4 * h->prof_n + 0] : nullptr;
-        h->kev1 = prof ? h->ev[4 * h->prof_n + 1] : nullptr;
+        kernel_events(h, prof);
         mppi_step_launch L{STEP_PRE | (fused ? STEP_FUSE : 0), x_dev, h->U_cur(), h->U_other(), u_dev, seq};
         L.ugr = ugr_in; L.utag = h->pre_tag; L.step_index = h->pre_step; L.ugr_out = fused ? ugr_out : nullptr;
-        const hipError_t e = launch_step(h, st, &L);
+        const hipError_t e = per_a(h, &mppi_unit_a::step, st, &L);
         h->kev0 = h->kev1 = nullptr;
         HIP_TRY(h, e);
     }
@@ -1063,7 +1036,7 @@ extern "C" mppi_status mppi_next_device(mppi_handle *h, const float *x_dev, floa
     MPPI_ENTER(h);
     TraceRange step_range(h, "mppi:step");
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    if (fuse_ok(h)) return fused_step(h, st, x_dev, u_dev);
+    if (rollout_route(h, SRC_PHILOX, nullptr, true) == ROUTE_STEP) return fused_step(h, st, x_dev, u_dev);
     int nrec = 0;
     mppi_status s = enqueue_partials(h, st, SRC_PHILOX, x_dev, nullptr, nullptr, &nrec);
     if (s != MPPI_OK) return s;
@@ -1110,9 +1083,9 @@ extern "C" mppi_status mppi_shard_cost_range(mppi_handle *h, const float *x_dev,
     h->norm_two_pass = 0;
     h->kev0 = h->kev1 = nullptr;
     HIP_TRY(h, ensure_record_layout(h, st, h->nb));
-    if (norm_fast(h)) HIP_TRY(h, launch_pc(h, st, x_dev)); // its records (at lambda) are overwritten by the second pass
+    if (norm_fast(h)) HIP_TRY(h, per_a(h, &mppi_unit_a::pc, st, x_dev)); // its records (at lambda) are overwritten by the second pass
     else if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, st, SRC_PHILOX, MODE_COST_ONLY, x_dev, h->U_cur(), nullptr, h->d_cost, h->d_part, nullptr));
-    else if (mlp) HIP_TRY(h, launch_mlp(h, st, SRC_PHILOX, MODE_COST_ONLY, x_dev, h->U_cur(), nullptr, h->d_cost));
+    else if (mlp) HIP_TRY(h, per_a(h, &mppi_unit_a::mlp, st, SRC_PHILOX, MODE_COST_ONLY, x_dev, h->U_cur(), nullptr, h->d_cost));
     else HIP_TRY(h, launch_tile(h, st, SRC_PHILOX, MODE_COST_ONLY, x_dev, h->U_cur(), nullptr, h->d_cost, h->d_part, nullptr));
     hipLaunchKernelGGL(k_cost_minmax, dim3(1), dim3(1024), 0, st, h->d_cost, h->K_local, h->d_mm, 0.0f, (float *)nullptr, range_dev);
     HIP_TRY(h, hipGetLastError());
@@ -1133,7 +1106,7 @@ extern "C" mppi_status mppi_shard_partial_normalized(mppi_handle *h, const float
     if (fast) { // the weights-only pass (PC_PASS_WEIGHTS) at the temperature of the agreed range (k_range_apply left it in d_mm[2]): the costs of
                 // mppi_shard_cost_range, the noise regenerated from the same Philox counters, records of the raw costs at that temperature
         h->pc_pass = PC_PASS_WEIGHTS; h->pc_range_given = 1;
-        const hipError_t le = launch_pc(h, st, x_dev);
+        const hipError_t le = per_a(h, &mppi_unit_a::pc, st, x_dev);
         h->pc_pass = PC_PASS_PLAIN; h->pc_range_given = 0;
         HIP_TRY(h, le);
         h->norm_two_pass = 1;
@@ -1407,7 +1380,7 @@ static mppi_status step_host(mppi_handle *h, const float *x, int n_x, const floa
     float *u_arg = h->d_pin + 2 * kMaxS;
     const bool spin_u = h->sync_spin && h->sg_window == 0; // with a sequence filter the step has one more kernel after u
     if (spin_u) for (int j = 0; j < h->a; ++j) uslot[j] = kUSentinel;
-    if (src == SRC_PHILOX && fuse_ok(h)) {
+    if (rollout_route(h, src, nullptr, true) == ROUTE_STEP) {
         mppi_status s = fused_step(h, h->stream, x_arg, u_arg);
         if (s != MPPI_OK) return s;
     } else {
@@ -1858,7 +1831,7 @@ extern "C" mppi_status mppi_rollout_cost(mppi_handle *h, const float *x, const f
     HIP_TRY(h, dx.up(x, h->s, h->stream)); HIP_TRY(h, dU.up(U, h->HA, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_eps, eps, sizeof(float) * (size_t)h->K_local * h->HA, hipMemcpyHostToDevice, h->stream));
     if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, h->stream, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
-    else if (h->hc.model_kind == MPPI_MODEL_MLP) HIP_TRY(h, launch_mlp(h, h->stream, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p));
+    else if (h->hc.model_kind == MPPI_MODEL_MLP) HIP_TRY(h, per_a(h, &mppi_unit_a::mlp, h->stream, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p));
     else HIP_TRY(h, launch_tile(h, h->stream, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
     HIP_TRY(h, dc.down(cost_out, h->K_local, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1928,30 +1901,6 @@ extern "C" mppi_status mppi_shift(const float *U, int tau, int a, const float *i
 // same config with cfg.seed = seeds[m], fed the same x, goal and sequence, on the same step counter: the batched rollout is the text of
 // k_rollout_pc (the point mass) or k_rollout_auv_pc (the Fossen AUV model) with per-member operands, with the instance that handle would
 // launch, and the batched finish is k_finish_cols' column_combine on the member's records over the same padded record count.
-static hipError_t launch_batch(mppi_handle *h, hipStream_t st, const float *x_dev)
-{
-    if (h->is_gen) return mppi_launch_batch_auv(h, st, x_dev);
-    switch (h->a) {
-    case 1: return mppi_launch_batch_a1(h, st, x_dev);
-    case 2: return mppi_launch_batch_a2(h, st, x_dev);
-    case 3: return mppi_launch_batch_a3(h, st, x_dev);
-    case 4: return mppi_launch_batch_a4(h, st, x_dev);
-    }
-    return hipErrorInvalidValue;
-}
-
-static hipError_t launch_batch_finish(mppi_handle *h, hipStream_t st, float *u_dev, hipEvent_t ev0, hipEvent_t ev1)
-{
-    if (h->is_gen) return mppi_launch_batch_finish_auv(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
-    switch (h->a) {
-    case 1: return mppi_launch_batch_finish_a1(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
-    case 2: return mppi_launch_batch_finish_a2(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
-    case 3: return mppi_launch_batch_finish_a3(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
-    case 4: return mppi_launch_batch_finish_a4(h, st, h->U_cur(), h->U_other(), u_dev, ev0, ev1);
-    }
-    return hipErrorInvalidValue;
-}
-
 // the Fossen AUV model on its two-wave rollout (k_rollout_auv_pc, every horizon) with the step's one pass: what k_rollout_auv_pc_batch runs
 static bool auv_batch_eligible(const mppi_handle *h)
 {
@@ -2061,12 +2010,13 @@ static mppi_status batch_step(mppi_handle *h, hipStream_t st, const float *x_dev
                                                        : "batched step: the horizon exceeds what this producer count serves (tau <= 132 with 3 producers)");
     TraceRange step_range(h, "mppi:batch_step");
     const bool prof = h->prof_n < h->prof_cap;
-    h->kev0 = prof ? h->ev[4 * h->prof_n + 0] : nullptr; // the dispatches' own begin / end
-    h->kev1 = prof ? h->ev[4 * h->prof_n + 1] : nullptr;
-    const hipError_t e = launch_batch(h, st, x_dev);
+    kernel_events(h, prof); // the dispatches' own begin / end
+    const hipError_t e = h->is_gen ? mppi_launch_batch_auv(h, st, x_dev) : per_a(h, &mppi_unit_a::batch, st, x_dev);
     h->kev0 = h->kev1 = nullptr;
     HIP_TRY(h, e);
-    HIP_TRY(h, launch_batch_finish(h, st, u_dev, prof ? h->ev[4 * h->prof_n + 2] : nullptr, prof ? h->ev[4 * h->prof_n + 3] : nullptr));
+    hipEvent_t f0 = prof ? h->ev[4 * h->prof_n + 2] : nullptr, f1 = prof ? h->ev[4 * h->prof_n + 3] : nullptr;
+    HIP_TRY(h, h->is_gen ? mppi_launch_batch_finish_auv(h, st, h->U_cur(), h->U_other(), u_dev, f0, f1)
+                         : per_a(h, &mppi_unit_a::batch_finish, st, (const float *)h->U_cur(), h->U_other(), u_dev, f0, f1));
     if (prof) { h->prof_stream = st; h->prof_n++; }
     h->U_advance();
     return MPPI_OK;

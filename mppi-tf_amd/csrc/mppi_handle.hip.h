@@ -8,6 +8,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -138,23 +139,70 @@ struct mppi_handle {
     size_t xchg_inbox_bytes() const { return sizeof(unsigned long long) * (xchg_step_slots() + (size_t)2 * shard_count); }
 };
 
-
 // The dynamic-LDS ceiling (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the (kernel instance, device) pair,
 // not to a handle: several handles, devices and host threads share one template instance. It is kept process-wide and
 // only ever RAISED (mppi_capi.hip), so a handle that needs less never lowers it under one that needs more.
 hipError_t mppi_raise_lds_ceiling(const void *kernel, int device, size_t bytes);
 
-// launchers: one definition per action dimension, each in its own object file
+// ---- launch policy shared by the launch units (each rule defined once) ---------------------------------------------------
+// slots per producer wave of k_rollout_pc / k_rollout_pc_batch / k_step_pc: the horizon's 4-step groups, spread over NP producers
+inline int mppi_pc_slots(int np, int H) { const int NG = (H + 3) / 4; return np == 3 ? (NG <= 18 ? 6 : 11) : (NG <= 20 ? 4 : 8); }
+// f(NSLOT) with NSLOT as a std::integral_constant: the slot count of the NP-producer instances that serves the horizon H
+template <int NP, typename F>
+auto mppi_with_slots(int H, F &&f)
+{
+    using std::integral_constant;
+    if constexpr (NP == 3) return mppi_pc_slots(3, H) == 6 ? f(integral_constant<int, 6>{}) : f(integral_constant<int, 11>{});
+    else return mppi_pc_slots(5, H) == 4 ? f(integral_constant<int, 4>{}) : f(integral_constant<int, 8>{});
+}
+// The balance word of k_rollout_pc / k_rollout_pc_batch / k_step_pc over a grid of `tiles` workgroups: one round of workgroups (<= 4 per
+// CU, all resident from the start) gets SIMD-true roles + progress priorities. Bit 0: on; bits 8..23: the generations' head starts
+// (pc_set_prio). Four workgroups per CU (the small-NSLOT instances): 10, 3, 3, 0 quarter chunks — r05's sweep on three boxes
+// (tools/tune_prio.py, profiles/r05_tune_prio.txt): kernel 15.05 -> 14.68 us at configs[2], 14.1 -> 13.4 at K = 49152, against r04's 9, 6,
+// 3, 0; two per CU (H > 80 at a = 3) keep r04's: the new ones cost 10 % there.
+inline int mppi_pc_balance(const mppi_handle *h, int A, int NSLOT, int tiles)
+{
+    const int bias = h->pc_bias >= 0 ? h->pc_bias : ((NSLOT * 4 * A <= 80) ? 0x033a : 0x0369);
+    return (tiles <= 4 * 256 && !h->pc_no_balance) ? (1 | (bias << 8)) : 0;
+}
+// SIMD-true roles of the two-tile workgroups (a network / pose wave and a cost / velocity wave per tile) while the whole grid of `wgs`
+// workgroups is resident in one round (MPPI_TUNE_PC_BALANCE = 0: roles by wave index, A/B)
+inline int mppi_two_tile_balance(const mppi_handle *h, int wgs) { return (wgs <= 2 * h->n_cu && !h->pc_no_balance) ? 1 : 0; }
+// the one-launch step on SEVEN producer waves (k_step_pc<A, 7, 3, ..>): H <= 84, unless MPPI_TUNE_FUSED_STEP = 2 keeps the six-wave workgroup
+inline bool mppi_step_seven(const mppi_handle *h) { return h->fuse_step != 2 && (h->H + 3) / 4 <= 21; }
+
+// ---- picks and launches -----------------------------------------------------------------------------------------------------------
+// A pick (one per kernel family, in the family's launch unit) is a pure function of the handle that returns the kernel instance a launch
+// serves, its name as rocprofv3 prints it and the geometry the template arguments decide; the launcher then launches exactly that.
+// The name is formatted once per instance from the template arguments that instantiate it (a function-local static of the instance's pick).
+template <typename... V>
+std::string mppi_fmt(const char *fmt, V... v) { char b[128]; std::snprintf(b, sizeof b, fmt, v...); return b; }
+inline const char *mppi_tf(bool b) { return b ? "true" : "false"; }
+// a pick of a family whose kernels take different argument lists: P holds one kernel pointer per list, and `slot` is set
+template <typename P, typename K>
+P mppi_pick_in(K P::*slot, K kern, const std::string &name, dim3 g, dim3 b, size_t lds = 0)
+{
+    P p; p.*slot = kern; p.name = name.c_str(); p.g = g; p.b = b; p.lds = lds; return p;
+}
+// f(DIAG) with DIAG as a std::bool_constant: the instance for an exactly diagonal Sigma or the one for a dense Sigma
+template <typename F>
+auto mppi_with_diag(const mppi_handle *h, F &&f) { return h->sigma_diag ? f(std::true_type{}) : f(std::false_type{}); }
+
+// One launch of a rollout kernel on the handle's kernel events (h->kev0 / kev1: the dispatch's own begin / end on a profiled step, else
+// none), after raising the instance's dynamic-LDS ceiling if it needs more than the default.
+template <typename... P, typename... Args>
+hipError_t mppi_launch(const mppi_handle *h, void (*kern)(P...), dim3 g, dim3 b, size_t lds, hipStream_t st, Args... args)
+{
+    if (hipError_t e = mppi_raise_lds_ceiling(reinterpret_cast<const void *>(kern), h->device, lds); e != hipSuccess) return e;
+    hipExtLaunchKernelGGL(kern, g, b, (uint32_t)lds, st, h->kev0, h->kev1, 0, args...);
+    return hipGetLastError();
+}
+
 #define MPPI_TILE_PARAMS mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, \
                          const float *eps, float *cost, float *part, float *noise_out
 #define MPPI_MLP_PARAMS mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, \
                         const float *eps, float *cost
 #define MPPI_PC_PARAMS mppi_handle *h, hipStream_t st, const float *x_dev
-#define MPPI_DECL_A(NAME, PARAMS) \
-    hipError_t NAME##1(PARAMS); hipError_t NAME##2(PARAMS); hipError_t NAME##3(PARAMS); hipError_t NAME##4(PARAMS);
-MPPI_DECL_A(mppi_launch_tile_a, MPPI_TILE_PARAMS)
-MPPI_DECL_A(mppi_launch_pc_a, MPPI_PC_PARAMS)
-MPPI_DECL_A(mppi_launch_mlp_a, MPPI_MLP_PARAMS)
 // one launch of k_step_pc (mppi_step.hip.h): mode = STEP_FUSE | STEP_ARM bits; the sequence it reads / writes is given explicitly
 // (an armed launch for step n+1 is enqueued before step n's bookkeeping is committed)
 struct mppi_step_launch {
@@ -163,19 +211,29 @@ struct mppi_step_launch {
     unsigned long long *ugr_out = nullptr; // STEP_PRE | STEP_FUSE: the next step's granules (the column waves write them)
 };
 #define MPPI_STEP_PARAMS mppi_handle *h, hipStream_t st, const mppi_step_launch *L
-MPPI_DECL_A(mppi_launch_step_a, MPPI_STEP_PARAMS)
-// the batched step (mppi_launch_batch.hip): every member's rollout in one launch, every member's finish in another
-MPPI_DECL_A(mppi_launch_batch_a, MPPI_PC_PARAMS)
 #define MPPI_BATCH_FINISH_PARAMS mppi_handle *h, hipStream_t st, const float *U_in, float *U_out, float *u_dev, hipEvent_t ev0, hipEvent_t ev1
-MPPI_DECL_A(mppi_launch_batch_finish_a, MPPI_BATCH_FINISH_PARAMS)
+// The entry points of the per-a launch units (mppi_launch_{tile,pc,mlp,step,batch}.hip): X(NAME, result, parameters) is defined as
+// mppi_NAME_a1 .. mppi_NAME_a4, one per action dimension, each in its own object file; the *_name entries name what the launch would run.
+// The batched step (mppi_launch_batch.hip): every member's rollout in one launch, every member's finish in another.
+#define MPPI_UNIT_ENTRIES(X)                                                                                                         \
+    X(tile, hipError_t, MPPI_TILE_PARAMS) X(pc, hipError_t, MPPI_PC_PARAMS) X(mlp, hipError_t, MPPI_MLP_PARAMS)                       \
+    X(step, hipError_t, MPPI_STEP_PARAMS) X(batch, hipError_t, MPPI_PC_PARAMS) X(batch_finish, hipError_t, MPPI_BATCH_FINISH_PARAMS) \
+    X(tile_name, const char *, const mppi_handle *h, int src, int mode) X(pc_name, const char *, const mppi_handle *h, int pass)      \
+    X(mlp_name, const char *, const mppi_handle *h, int src) X(step_name, const char *, const mppi_handle *h, int mode)               \
+    X(batch_name, const char *, const mppi_handle *h)
+#define MPPI_DECL_A(NAME, R, ...) R mppi_##NAME##_a1(__VA_ARGS__); R mppi_##NAME##_a2(__VA_ARGS__); R mppi_##NAME##_a3(__VA_ARGS__); R mppi_##NAME##_a4(__VA_ARGS__);
+#define MPPI_MEMBER(NAME, R, ...) R (*NAME)(__VA_ARGS__);
+MPPI_UNIT_ENTRIES(MPPI_DECL_A)
+struct mppi_unit_a { MPPI_UNIT_ENTRIES(MPPI_MEMBER) }; // one row per action dimension (mppi_capi.hip holds the table)
 #undef MPPI_DECL_A
+#undef MPPI_MEMBER
 // the 13-state AUV family (mppi_launch_gen.hip)
 const char *mppi_gen_fill(mppi_handle *h, const mppi_config *cfg); // NULL = ok, else why the config is invalid
 hipError_t mppi_gen_upload(mppi_handle *h);
 void mppi_gen_destroy(mppi_handle *h);
 hipError_t mppi_launch_gen(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, const float *eps,
                            float *cost, float *part, float *noise_out);
-const char *mppi_gen_kernel_name(const mppi_handle *h);
+const char *mppi_gen_name(const mppi_handle *h, int mode); // the instance mppi_launch_gen runs for `mode` without a noise export
 hipError_t mppi_gen_model_step(mppi_handle *h, hipStream_t st, const float *x, int kx, const float *v, int k, float *scratch, float *out_next);
 hipError_t mppi_gen_costs(mppi_handle *h, hipStream_t st, const float *x, const float *u, const float *eps, int k, float *os, float *oa, float *ot);
 hipError_t mppi_gen_auv_pieces(mppi_handle *h, hipStream_t st, const float *x, const float *u, int k, float *out);
@@ -185,5 +243,6 @@ const void *mppi_gen_dev_consts(const mppi_handle *h); // the handle's GenConsts
 // every member's finish in another (k_finish_cols_batch<6>)
 hipError_t mppi_launch_batch_auv(MPPI_PC_PARAMS);
 hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS);
+const char *mppi_batch_auv_name(const mppi_handle *h);
 #define MPPI_CAT_(a, b) a##b
 #define MPPI_CAT(a, b) MPPI_CAT_(a, b)

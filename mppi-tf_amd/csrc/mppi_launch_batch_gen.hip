@@ -5,23 +5,27 @@
 #include "mppi_handle.hip.h"
 #include "mppi_gen.hip.h"
 
+static auto pick_batch_auv(const mppi_handle *h)
+{
+    struct Pick { decltype(&k_rollout_auv_pc_batch<false>) kern; const char *name; };
+    return mppi_with_diag(h, [&](auto d) {
+        static const std::string name = mppi_fmt("mppi::k_rollout_auv_pc_batch<%s>", mppi_tf(d));
+        return Pick{k_rollout_auv_pc_batch<decltype(d)::value>, name.c_str()};
+    });
+}
+
 // Every member's rollouts: one flat grid of B * W workgroups, W = (nb + 1) / 2 per member (two tiles per workgroup), as mppi_launch_gen's
 // k_rollout_auv_pc launch per member. The SIMD-true roles are enabled by the TOTAL workgroup count, as the lone launcher decides them.
 hipError_t mppi_launch_batch_auv(MPPI_PC_PARAMS)
 {
-    const int W = (h->nb + 1) / 2;
-    const int wgs = W * h->batch;
-    const int balance = (wgs <= 2 * h->n_cu && !h->pc_no_balance) ? 1 : 0;
+    const int wgs = (h->nb + 1) / 2 * h->batch;
     const PcBatchArgs bt{h->d_seeds, h->d_goals, h->nb, h->HA + h->a, h->nbp * (2 + h->HA)};
     const GenConsts *G = static_cast<const GenConsts *>(mppi_gen_dev_consts(h));
-    if (h->sigma_diag)
-        hipExtLaunchKernelGGL(k_rollout_auv_pc_batch<true>, dim3(wgs), dim3(kAuvPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, G,
-                              x_dev, h->U_cur(), (const unsigned long long *)h->d_step, h->d_cost, h->d_part, 1, h->nbp, h->nb, balance, bt);
-    else
-        hipExtLaunchKernelGGL(k_rollout_auv_pc_batch<false>, dim3(wgs), dim3(kAuvPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, G,
-                              x_dev, h->U_cur(), (const unsigned long long *)h->d_step, h->d_cost, h->d_part, 1, h->nbp, h->nb, balance, bt);
-    return hipGetLastError();
+    return mppi_launch(h, pick_batch_auv(h).kern, dim3(wgs), dim3(kAuvPcThreads), 0, st, h->dC, G, x_dev, h->U_cur(), h->d_step, h->d_cost,
+                       h->d_part, 1, h->nbp, h->nb, mppi_two_tile_balance(h, wgs), bt);
 }
+
+const char *mppi_batch_auv_name(const mppi_handle *h) { return pick_batch_auv(h).name; }
 
 // the finish of every member: one workgroup per (member, column); reads U_in, writes U_out and u_dev [B][6]
 hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS)

@@ -151,114 +151,88 @@ void mppi_gen_destroy(mppi_handle *h)
     h->gen = nullptr;
 }
 
-// rollouts of a 13-state handle: one wave per 64-rollout tile
+// the instance of a 13-state rollout, by argument list (exactly one pointer is set), and its geometry
+struct GenPick {
+    const char *name = nullptr;
+    dim3 g, b;
+    size_t lds = 0;
+    decltype(&k_rollout_gen<GEN_MODEL_AUV, 32, false>) one = nullptr;  // k_rollout_gen: one wave per tile, every mode
+    decltype(&k_rollout_nnauv32<false>) mfma = nullptr;                 // the learned models on the matrix cores, one tile per workgroup
+    decltype(&k_rollout_nnauv_pc<false>) pipe = nullptr;                // ... two-wave pipelines, two tiles per workgroup (+ tile count, balance)
+    decltype(&k_rollout_auv_pc<false>) auv = nullptr;                   // the Fossen model's two-wave pipeline (no network)
+};
+
+// the instance mppi_launch_gen runs for (mode, a noise export or not)
+static GenPick pick_gen(const mppi_handle *h, int mode, bool noise_out)
+{
+    using std::integral_constant;
+    const int nb = h->nb, wgs = (h->nb + 1) / 2;
+    const int mk = h->hc.model_kind;
+    const bool fast_mode = (mode == MODE_ROLLOUT || mode == MODE_COST_ONLY) && !noise_out;
+    auto hid = [&](auto f) { return h->mlp_small == 16 ? f(integral_constant<int, 16>{}) : f(integral_constant<int, 32>{}); };
+    // Dense(32) NNAUVModel: the matrix-core kernel (rollouts and cost-only passes; the record-from-given-costs / noise-export modes
+    // and MPPI_TUNE_MLP32_VALU stay on the vector-ALU kernel)
+    if (mk == MPPI_MODEL_NN_AUV && h->mlp_small == 32 && h->mlp32_valu != 1 && fast_mode)
+        return mppi_with_diag(h, [&](auto d) {
+            if (h->mlp_bx3) { // MPPI_FLAG_MLP_BF16X3: the bf16 matrix cores, every operand split in two
+                static const std::string name = mppi_fmt("mppi::k_rollout_nnauv32_bx3<%s>", mppi_tf(d));
+                return mppi_pick_in(&GenPick::mfma, k_rollout_nnauv32_bx3<decltype(d)::value>, name, dim3(nb), dim3(kNnauv32Threads));
+            }
+            if (h->mlp32_valu == 0) { // default (r04): the two-wave pipeline (network wave + cost wave per tile, two tiles per workgroup)
+                static const std::string name = mppi_fmt("mppi::k_rollout_nnauv_pc<%s>", mppi_tf(d));
+                return mppi_pick_in(&GenPick::pipe, k_rollout_nnauv_pc<decltype(d)::value>, name, dim3(wgs), dim3(kNnauvPcThreads));
+            }
+            static const std::string name = mppi_fmt("mppi::k_rollout_nnauv32<%s>", mppi_tf(d)); // MPPI_TUNE_MLP32_VALU = 2: one wave per 32 rollouts (A/B timing)
+            return mppi_pick_in(&GenPick::mfma, k_rollout_nnauv32<decltype(d)::value>, name, dim3(nb), dim3(kNnauv32Threads));
+        });
+    // NNAUVModelSpeed: the matrix-core kernel for rollouts and cost-only passes (r04); the other modes and MPPI_TUNE_MLP32_VALU stay
+    // on the lane-per-rollout kernel
+    if (mk == MPPI_MODEL_NN_AUV_SPEED && h->mlp32_valu != 1 && fast_mode)
+        return hid([&](auto w) {
+            return mppi_with_diag(h, [&](auto d) {
+                constexpr int W = decltype(w)::value;
+                if (h->mlp32_valu == 2) { // MPPI_TUNE_MLP32_VALU = 2: the one-wave-per-32-rollouts matrix-core kernel (A/B timing)
+                    static const std::string name = mppi_fmt("mppi::k_rollout_nnspeed32<%d, %s>", W, mppi_tf(d));
+                    return mppi_pick_in(&GenPick::mfma, k_rollout_nnspeed32<W, decltype(d)::value>, name, dim3(nb), dim3(kNnauv32Threads));
+                }
+                // default: the two-wave pipeline (network wave + pose wave per tile, two tiles per workgroup)
+                static const std::string name = mppi_fmt("mppi::k_rollout_nnspeed_pc<%d, %s>", W, mppi_tf(d));
+                return mppi_pick_in(&GenPick::pipe, k_rollout_nnspeed_pc<W, decltype(d)::value>, name, dim3(wgs), dim3(kNnspeedPcThreads));
+            });
+        });
+    // Fossen AUVModel: the two-wave pipeline (pose wave + velocity wave per tile, r04) for rollouts and cost-only passes; the other modes
+    // and MPPI_TUNE_GEN_ONE_WAVE stay on the one-wave-per-tile kernel
+    if (mk == MPPI_MODEL_AUV && !h->gen_one_wave && fast_mode)
+        return mppi_with_diag(h, [&](auto d) {
+            static const std::string name = mppi_fmt("mppi::k_rollout_auv_pc<%s>", mppi_tf(d));
+            return mppi_pick_in(&GenPick::auv, k_rollout_auv_pc<decltype(d)::value>, name, dim3(wgs), dim3(kAuvPcThreads));
+        });
+    // one wave per 64-rollout tile
+    auto one = [&](auto model, auto w) {
+        return mppi_with_diag(h, [&](auto d) {
+            constexpr int MODEL = decltype(model)::value, W = decltype(w)::value;
+            static const std::string name = mppi_fmt("mppi::k_rollout_gen<%d, %d, %s>", MODEL, W, mppi_tf(d));
+            return mppi_pick_in(&GenPick::one, k_rollout_gen<MODEL, W, decltype(d)::value>, name, dim3(nb), dim3(64));
+        });
+    };
+    if (mk == MPPI_MODEL_AUV) return one(integral_constant<int, GEN_MODEL_AUV>{}, integral_constant<int, 32>{});
+    if (mk == MPPI_MODEL_NN_AUV_SPEED) return hid([&](auto w) { return one(integral_constant<int, GEN_MODEL_NNAUV_SPEED>{}, w); });
+    return hid([&](auto w) { return one(integral_constant<int, GEN_MODEL_NNAUV>{}, w); });
+}
+
+const char *mppi_gen_name(const mppi_handle *h, int mode) { return pick_gen(h, mode, false).name; }
+
+// rollouts of a 13-state handle
 hipError_t mppi_launch_gen(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, const float *eps,
                            float *cost, float *part, float *noise_out)
 {
-    const GenState *g = gs(h);
-    const dim3 grid(h->nb), block(64);
-#define MPPI_GEN_L(MODEL, HID)                                                                                                     \
-    do {                                                                                                                           \
-        if (h->sigma_diag)                                                                                                         \
-            hipExtLaunchKernelGGL((k_rollout_gen<MODEL, HID, true>), grid, block, 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const GenConsts *)g->dG, \
-                                  (const MlpDev *)h->dM, h->small_args, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, part, noise_out, \
-                                  src, mode, 1, h->nbp);                                                                            \
-        else                                                                                                                       \
-            hipExtLaunchKernelGGL((k_rollout_gen<MODEL, HID, false>), grid, block, 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const GenConsts *)g->dG, \
-                                  (const MlpDev *)h->dM, h->small_args, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, part, noise_out, \
-                                  src, mode, 1, h->nbp);                                                                            \
-    } while (0)
-#define MPPI_NNAUV32_L(KERN)                                                                                                       \
-    hipExtLaunchKernelGGL(KERN, grid, dim3(kNnauv32Threads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const GenConsts *)g->dG,        \
-                          (const MlpDev *)h->dM, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, part, src, mode, 1, h->nbp)
-    // Dense(32) NNAUVModel: the matrix-core kernel (rollouts and cost-only passes; the record-from-given-costs / noise-export modes
-    // and MPPI_TUNE_MLP32_VALU stay on the vector-ALU kernel)
-    if (h->hc.model_kind == MPPI_MODEL_NN_AUV && h->mlp_small == 32 && h->mlp32_valu != 1 && (mode == MODE_ROLLOUT || mode == MODE_COST_ONLY) && noise_out == nullptr) {
-        if (h->mlp_bx3) { // MPPI_FLAG_MLP_BF16X3: the bf16 matrix cores, every operand split in two
-            if (h->sigma_diag) MPPI_NNAUV32_L(k_rollout_nnauv32_bx3<true>);
-            else MPPI_NNAUV32_L(k_rollout_nnauv32_bx3<false>);
-        } else if (h->mlp32_valu == 0) { // default (r04): the two-wave pipeline (network wave + cost wave per tile, two tiles per workgroup)
-            const int wgs = (h->nb + 1) / 2;
-            const int balance = (wgs <= 2 * h->n_cu && !h->pc_no_balance) ? 1 : 0; // (MPPI_TUNE_PC_BALANCE = 0: roles by wave index, A/B)
-            if (h->sigma_diag)
-                hipExtLaunchKernelGGL(k_rollout_nnauv_pc<true>, dim3(wgs), dim3(kNnauvPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const GenConsts *)g->dG,
-                                      (const MlpDev *)h->dM, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
-            else
-                hipExtLaunchKernelGGL(k_rollout_nnauv_pc<false>, dim3(wgs), dim3(kNnauvPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const GenConsts *)g->dG,
-                                      (const MlpDev *)h->dM, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
-        } else { // MPPI_TUNE_MLP32_VALU = 2: one wave per 32 rollouts (A/B timing)
-            if (h->sigma_diag) MPPI_NNAUV32_L(k_rollout_nnauv32<true>);
-            else MPPI_NNAUV32_L(k_rollout_nnauv32<false>);
-        }
-        return hipGetLastError();
-    }
-    // NNAUVModelSpeed: the matrix-core kernel for rollouts and cost-only passes (r04); the other modes and MPPI_TUNE_MLP32_VALU stay
-    // on the lane-per-rollout kernel
-    if (h->hc.model_kind == MPPI_MODEL_NN_AUV_SPEED && h->mlp32_valu != 1 && (mode == MODE_ROLLOUT || mode == MODE_COST_ONLY) && noise_out == nullptr) {
-        if (h->mlp32_valu == 2) { // MPPI_TUNE_MLP32_VALU = 2: the one-wave-per-32-rollouts matrix-core kernel (A/B timing)
-            if (h->mlp_small == 16) { if (h->sigma_diag) MPPI_NNAUV32_L((k_rollout_nnspeed32<16, true>)); else MPPI_NNAUV32_L((k_rollout_nnspeed32<16, false>)); }
-            else { if (h->sigma_diag) MPPI_NNAUV32_L((k_rollout_nnspeed32<32, true>)); else MPPI_NNAUV32_L((k_rollout_nnspeed32<32, false>)); }
-            return hipGetLastError();
-        }
-        // default: the two-wave pipeline (network wave + pose wave per tile, two tiles per workgroup)
-        const int wgs = (h->nb + 1) / 2;
-        const int balance = (wgs <= 2 * h->n_cu && !h->pc_no_balance) ? 1 : 0; // (MPPI_TUNE_PC_BALANCE = 0: roles by wave index, A/B) // SIMD-true roles only while the whole grid is resident in one round
-#define MPPI_NNSPEED_PC_L(KERN)                                                                                                    \
-    hipExtLaunchKernelGGL(KERN, dim3(wgs), dim3(kNnspeedPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const GenConsts *)g->dG, \
-                          (const MlpDev *)h->dM, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance)
-        if (h->mlp_small == 16) { if (h->sigma_diag) MPPI_NNSPEED_PC_L((k_rollout_nnspeed_pc<16, true>)); else MPPI_NNSPEED_PC_L((k_rollout_nnspeed_pc<16, false>)); }
-        else { if (h->sigma_diag) MPPI_NNSPEED_PC_L((k_rollout_nnspeed_pc<32, true>)); else MPPI_NNSPEED_PC_L((k_rollout_nnspeed_pc<32, false>)); }
-#undef MPPI_NNSPEED_PC_L
-        return hipGetLastError();
-    }
-#undef MPPI_NNAUV32_L
-    // Fossen AUVModel: the two-wave pipeline (pose wave + velocity wave per tile, r04) for rollouts and cost-only passes; the other modes
-    // and MPPI_TUNE_GEN_ONE_WAVE stay on the one-wave-per-tile kernel
-    if (h->hc.model_kind == MPPI_MODEL_AUV && !h->gen_one_wave && (mode == MODE_ROLLOUT || mode == MODE_COST_ONLY) && noise_out == nullptr) {
-        const int wgs = (h->nb + 1) / 2;
-        const int balance = (wgs <= 2 * h->n_cu && !h->pc_no_balance) ? 1 : 0; // (MPPI_TUNE_PC_BALANCE = 0: roles by wave index, A/B)
-        if (h->sigma_diag)
-            hipExtLaunchKernelGGL(k_rollout_auv_pc<true>, dim3(wgs), dim3(kAuvPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const GenConsts *)g->dG,
-                                  x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
-        else
-            hipExtLaunchKernelGGL(k_rollout_auv_pc<false>, dim3(wgs), dim3(kAuvPcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const GenConsts *)g->dG,
-                                  x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
-        return hipGetLastError();
-    }
-    if (h->hc.model_kind == MPPI_MODEL_AUV) MPPI_GEN_L(GEN_MODEL_AUV, 32);
-    else if (h->hc.model_kind == MPPI_MODEL_NN_AUV_SPEED) {
-        if (h->mlp_small == 16) MPPI_GEN_L(GEN_MODEL_NNAUV_SPEED, 16);
-        else MPPI_GEN_L(GEN_MODEL_NNAUV_SPEED, 32);
-    } else if (h->mlp_small == 16) MPPI_GEN_L(GEN_MODEL_NNAUV, 16);
-    else MPPI_GEN_L(GEN_MODEL_NNAUV, 32);
-#undef MPPI_GEN_L
-    return hipGetLastError();
-}
-
-const char *mppi_gen_kernel_name(const mppi_handle *h)
-{
-    const bool d = h->sigma_diag != 0; // the last template argument: exactly diagonal Sigma (as the profiler spells the instance)
-    if (h->hc.model_kind == MPPI_MODEL_AUV) {
-        if (!h->gen_one_wave) return d ? "mppi::k_rollout_auv_pc<true>" : "mppi::k_rollout_auv_pc<false>";
-        return d ? "mppi::k_rollout_gen<0, 32, true>" : "mppi::k_rollout_gen<0, 32, false>";
-    }
-    if (h->hc.model_kind == MPPI_MODEL_NN_AUV_SPEED) {
-        if (h->mlp32_valu == 0)
-            return h->mlp_small == 16 ? (d ? "mppi::k_rollout_nnspeed_pc<16, true>" : "mppi::k_rollout_nnspeed_pc<16, false>")
-                                      : (d ? "mppi::k_rollout_nnspeed_pc<32, true>" : "mppi::k_rollout_nnspeed_pc<32, false>");
-        if (h->mlp32_valu == 2)
-            return h->mlp_small == 16 ? (d ? "mppi::k_rollout_nnspeed32<16, true>" : "mppi::k_rollout_nnspeed32<16, false>")
-                                      : (d ? "mppi::k_rollout_nnspeed32<32, true>" : "mppi::k_rollout_nnspeed32<32, false>");
-        return h->mlp_small == 16 ? (d ? "mppi::k_rollout_gen<2, 16, true>" : "mppi::k_rollout_gen<2, 16, false>")
-                                  : (d ? "mppi::k_rollout_gen<2, 32, true>" : "mppi::k_rollout_gen<2, 32, false>");
-    }
-    if (h->mlp_small == 32 && h->mlp32_valu != 1) {
-        if (h->mlp_bx3) return d ? "mppi::k_rollout_nnauv32_bx3<true>" : "mppi::k_rollout_nnauv32_bx3<false>";
-        if (h->mlp32_valu == 0) return d ? "mppi::k_rollout_nnauv_pc<true>" : "mppi::k_rollout_nnauv_pc<false>";
-        return d ? "mppi::k_rollout_nnauv32<true>" : "mppi::k_rollout_nnauv32<false>";
-    }
-    return h->mlp_small == 16 ? (d ? "mppi::k_rollout_gen<1, 16, true>" : "mppi::k_rollout_gen<1, 16, false>")
-                              : (d ? "mppi::k_rollout_gen<1, 32, true>" : "mppi::k_rollout_gen<1, 32, false>");
+    const GenPick p = pick_gen(h, mode, noise_out != nullptr);
+    const GenConsts *G = gs(h)->dG;
+    if (p.one) return mppi_launch(h, p.one, p.g, p.b, 0, st, h->dC, G, h->dM, h->small_args, x_dev, U_dev, eps, h->d_step, cost, part, noise_out, src, mode, 1, h->nbp);
+    if (p.mfma) return mppi_launch(h, p.mfma, p.g, p.b, 0, st, h->dC, G, h->dM, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp);
+    const int balance = mppi_two_tile_balance(h, (int)p.g.x);
+    if (p.pipe) return mppi_launch(h, p.pipe, p.g, p.b, 0, st, h->dC, G, h->dM, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
+    return mppi_launch(h, p.auv, p.g, p.b, 0, st, h->dC, G, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
 }
 
 // NNAUVModel.build_step_graph in the reference's plain order (mul and add rounded separately, input index ascending, division by

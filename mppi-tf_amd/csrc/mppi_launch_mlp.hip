@@ -5,93 +5,80 @@
 #error "compile with -DMPPI_UNIT_A=<action dimension 1..4> (mppi-tf_amd/build.py)"
 #endif
 
-// learned-model rollouts (k_rollout_mlp): 64 rollouts per workgroup of 8 waves
+// the instance, by argument list (exactly one pointer is set), and its geometry
+struct MlpPick {
+    const char *name = nullptr;
+    dim3 g, b;
+    size_t lds = 0;
+    decltype(&k_rollout_mlp<MPPI_UNIT_A, false>) plain = nullptr;              // k_rollout_mlp, _mlp32, _mlp32_bx3
+    decltype(&k_rollout_mlp32_pc<MPPI_UNIT_A, false>) pipe = nullptr;          // ... + (tile count, balance): k_rollout_mlp32_pc
+    decltype(&k_rollout_mlp_small<MPPI_UNIT_A, 16>) small = nullptr;           // ... + the scalar-cache weights: k_rollout_mlp_small
+    decltype(&k_rollout_mlp_bx3<MPPI_UNIT_A, false, SRC_HBM>) nosrc = nullptr; // the noise source a template argument: k_rollout_mlp2, _mlp_bx3
+};
+
 template <int A>
-static hipError_t launch_mlp_a(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev,
-                               const float *eps, float *cost)
+static MlpPick pick_mlp(const mppi_handle *h, int src)
 {
-    const size_t lds = (h->mlp_v2 ? mlp2_lds_floats(2 * A, A, h->H) : mlp_lds_floats(2 * A, A)) * 4;
-    const dim3 g(h->mlp_v2 ? std::min(h->nb_mlp, h->n_cu) : h->nb_mlp), b(h->mlp_v2 ? kMlp2Threads : kMlpThreads);
-    if (mode != MODE_ROLLOUT && mode != MODE_COST_ONLY) return hipErrorInvalidValue;
+    const int nb = h->nb_mlp;
     if (h->mlp_small == 32 && h->mlp_bx3) { // ... on the bf16 matrix cores, every operand split in two (MPPI_FLAG_MLP_BF16X3)
-        hipExtLaunchKernelGGL((k_rollout_mlp32_bx3<A>), dim3(h->nb_mlp), dim3(kMlp32Threads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC,
-                              (const MlpDev *)h->dM, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
-        return hipGetLastError();
+        static const std::string name = mppi_fmt("mppi::k_rollout_mlp32_bx3<%d>", A);
+        return mppi_pick_in(&MlpPick::plain, k_rollout_mlp32_bx3<A>, name, dim3(nb), dim3(kMlp32Threads));
     }
-    if (h->mlp_small == 32 && h->mlp32_valu == 0) { // default (r04): the two-wave pipeline (network wave + cost wave per tile, two tiles per workgroup)
-        const int wgs = (h->nb_mlp + 1) / 2;
-        const int balance = (wgs <= 2 * h->n_cu && !h->pc_no_balance) ? 1 : 0; // SIMD-true roles while the whole grid is resident in one round
-        if (h->sigma_diag)
-            hipExtLaunchKernelGGL((k_rollout_mlp32_pc<A, true>), dim3(wgs), dim3(kMlp32PcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC,
-                                  (const MlpDev *)h->dM, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, h->d_part, src, mode, 1, h->nbp, h->nb_mlp, balance);
-        else
-            hipExtLaunchKernelGGL((k_rollout_mlp32_pc<A, false>), dim3(wgs), dim3(kMlp32PcThreads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC,
-                                  (const MlpDev *)h->dM, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, h->d_part, src, mode, 1, h->nbp, h->nb_mlp, balance);
-        return hipGetLastError();
-    }
+    if (h->mlp_small == 32 && h->mlp32_valu == 0) // default (r04): the two-wave pipeline (network wave + cost wave per tile, two tiles per workgroup)
+        return mppi_with_diag(h, [&](auto d) {
+            static const std::string name = mppi_fmt("mppi::k_rollout_mlp32_pc<%d, %s>", A, mppi_tf(d));
+            return mppi_pick_in(&MlpPick::pipe, k_rollout_mlp32_pc<A, decltype(d)::value>, name, dim3((nb + 1) / 2), dim3(kMlp32PcThreads));
+        });
     if (h->mlp_small == 32 && h->mlp32_valu == 2) { // MPPI_TUNE_MLP32_VALU = 2: one wave per 32 rollouts, 2 waves per tile (A/B timing)
-        hipExtLaunchKernelGGL((k_rollout_mlp32<A>), dim3(h->nb_mlp), dim3(kMlp32Threads), 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC,
-                              (const MlpDev *)h->dM, x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
-        return hipGetLastError();
+        static const std::string name = mppi_fmt("mppi::k_rollout_mlp32<%d>", A);
+        return mppi_pick_in(&MlpPick::plain, k_rollout_mlp32<A>, name, dim3(nb), dim3(kMlp32Threads));
     }
     if (h->mlp_small) { // one wave = one 64-rollout tile, weights through the scalar cache
-        const dim3 gs(h->nb_mlp), bs(64);
-        if (h->mlp_small == 16)
-            hipExtLaunchKernelGGL((k_rollout_mlp_small<A, 16>), gs, bs, 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const MlpDev *)h->dM, h->small_args,
-                                  x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
-        else
-            hipExtLaunchKernelGGL((k_rollout_mlp_small<A, 32>), gs, bs, 0, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const MlpDev *)h->dM, h->small_args,
-                                  x_dev, U_dev, eps, (const unsigned long long *)h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
-        return hipGetLastError();
+        auto small = [&](auto hid) {
+            static const std::string name = mppi_fmt("mppi::k_rollout_mlp_small<%d, %d>", A, decltype(hid)::value);
+            return mppi_pick_in(&MlpPick::small, k_rollout_mlp_small<A, decltype(hid)::value>, name, dim3(nb), dim3(64));
+        };
+        return h->mlp_small == 16 ? small(std::integral_constant<int, 16>{}) : small(std::integral_constant<int, 32>{});
     }
-#define MPPI_MLP_L(KERN, BIT)                                                                                           \
-    do {                                                                                                                \
-        auto kern = KERN;                                                                                               \
-        if (hipError_t e_ = mppi_raise_lds_ceiling(reinterpret_cast<const void *>(kern), h->device, lds); e_ != hipSuccess) return e_; \
-        hipExtLaunchKernelGGL(kern, g, b, (uint32_t)lds, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const MlpDev *)h->dM, x_dev, U_dev, eps, \
-                              (const unsigned long long *)h->d_step, cost, h->d_part, src, mode, 1, h->nbp);                \
-    } while (0)
-    if (h->mlp_bx3) { // one tile-walking workgroup of 4 waves per CU
-        const size_t ldsp = bx3_lds_floats(2 * A, A, h->H) * 4;
-        const dim3 gp(std::min(h->nb_mlp, h->n_cu)), bp(kBx3Threads);
-#define MPPI_BX3P_L(KERN)                                                                                               \
-    do {                                                                                                                \
-        auto kern = KERN;                                                                                               \
-        if (hipError_t e_ = mppi_raise_lds_ceiling(reinterpret_cast<const void *>(kern), h->device, ldsp); e_ != hipSuccess) return e_; \
-        hipExtLaunchKernelGGL(kern, gp, bp, (uint32_t)ldsp, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const MlpDev *)h->dM, x_dev, U_dev, eps, \
-                              (const unsigned long long *)h->d_step, cost, h->d_part, mode, 1, h->nbp);                     \
-    } while (0)
-        if (src == SRC_PHILOX) {
-            if (h->sigma_diag) MPPI_BX3P_L((k_rollout_mlp_bx3<A, true, SRC_PHILOX>));
-            else MPPI_BX3P_L((k_rollout_mlp_bx3<A, false, SRC_PHILOX>));
-        } else if (src == SRC_HBM) {
-            MPPI_BX3P_L((k_rollout_mlp_bx3<A, false, SRC_HBM>));
-        } else return hipErrorInvalidValue;
-#undef MPPI_BX3P_L
-    } else if (h->mlp_v2) {
-        if constexpr (A <= 3) {
-#define MPPI_MLP2_L(KERN, BIT)                                                                                          \
-    do {                                                                                                                \
-        auto kern = KERN;                                                                                               \
-        if (hipError_t e_ = mppi_raise_lds_ceiling(reinterpret_cast<const void *>(kern), h->device, lds); e_ != hipSuccess) return e_; \
-        hipExtLaunchKernelGGL(kern, g, b, (uint32_t)lds, st, h->kev0, h->kev1, 0, (const DevConsts *)h->dC, (const MlpDev *)h->dM, x_dev, U_dev, eps, \
-                              (const unsigned long long *)h->d_step, cost, h->d_part, mode, 1, h->nbp);                     \
-    } while (0)
-            if (src == SRC_PHILOX) {
-                if (h->sigma_diag) MPPI_MLP2_L((k_rollout_mlp2<A, true, SRC_PHILOX>), 32);
-                else MPPI_MLP2_L((k_rollout_mlp2<A, false, SRC_PHILOX>), 64);
-            } else if (src == SRC_HBM) { // injected noise (API helpers, tests): one instance, the dense-Sigma arithmetic
-                MPPI_MLP2_L((k_rollout_mlp2<A, false, SRC_HBM>), 256); // (exact for a diagonal Sigma too: it adds 0 * z terms)
-            } else return hipErrorInvalidValue;
-#undef MPPI_MLP2_L
-        } else return hipErrorInvalidValue;
-    } else if (h->sigma_diag) MPPI_MLP_L((k_rollout_mlp<A, true>), 2);
-    else MPPI_MLP_L((k_rollout_mlp<A, false>), 4);
-#undef MPPI_MLP_L
-    return hipGetLastError();
+    // the exact-fp32 2x256 network. Injected noise (API helpers, tests) runs one instance, the dense-Sigma arithmetic (exact for a
+    // diagonal Sigma too: it adds 0 * z terms)
+    auto by_src = [&](auto make) {
+        if (src == SRC_PHILOX) return mppi_with_diag(h, [&](auto d) { return make(d, std::integral_constant<int, SRC_PHILOX>{}); });
+        if (src == SRC_HBM) return make(std::false_type{}, std::integral_constant<int, SRC_HBM>{});
+        return MlpPick{};
+    };
+    if (h->mlp_bx3) // one tile-walking workgroup of 4 waves per CU
+        return by_src([&](auto d, auto s) {
+            static const std::string name = mppi_fmt("mppi::k_rollout_mlp_bx3<%d, %s, %d>", A, mppi_tf(d), decltype(s)::value);
+            return mppi_pick_in(&MlpPick::nosrc, k_rollout_mlp_bx3<A, decltype(d)::value, decltype(s)::value>, name, dim3(std::min(nb, h->n_cu)),
+                            dim3(kBx3Threads), bx3_lds_floats(2 * A, A, h->H) * 4);
+        });
+    if (h->mlp_v2) {
+        if constexpr (A <= 3)
+            return by_src([&](auto d, auto s) {
+                static const std::string name = mppi_fmt("mppi::k_rollout_mlp2<%d, %s, %d>", A, mppi_tf(d), decltype(s)::value);
+                return mppi_pick_in(&MlpPick::nosrc, k_rollout_mlp2<A, decltype(d)::value, decltype(s)::value>, name, dim3(std::min(nb, h->n_cu)),
+                                dim3(kMlp2Threads), mlp2_lds_floats(2 * A, A, h->H) * 4);
+            });
+        return MlpPick{};
+    }
+    return mppi_with_diag(h, [&](auto d) {
+        static const std::string name = mppi_fmt("mppi::k_rollout_mlp<%d, %s>", A, mppi_tf(d));
+        return mppi_pick_in(&MlpPick::plain, k_rollout_mlp<A, decltype(d)::value>, name, dim3(nb), dim3(kMlpThreads), mlp_lds_floats(2 * A, A) * 4);
+    });
 }
 
-hipError_t MPPI_CAT(mppi_launch_mlp_a, MPPI_UNIT_A)(MPPI_MLP_PARAMS)
+hipError_t MPPI_CAT(mppi_mlp_a, MPPI_UNIT_A)(MPPI_MLP_PARAMS)
 {
-    return launch_mlp_a<MPPI_UNIT_A>(h, st, src, mode, x_dev, U_dev, eps, cost);
+    if (mode != MODE_ROLLOUT && mode != MODE_COST_ONLY) return hipErrorInvalidValue;
+    const MlpPick p = pick_mlp<MPPI_UNIT_A>(h, src);
+    if (p.plain) return mppi_launch(h, p.plain, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
+    if (p.pipe)
+        return mppi_launch(h, p.pipe, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp, h->nb_mlp,
+                           mppi_two_tile_balance(h, (int)p.g.x));
+    if (p.small) return mppi_launch(h, p.small, p.g, p.b, p.lds, st, h->dC, h->dM, h->small_args, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
+    if (p.nosrc) return mppi_launch(h, p.nosrc, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, mode, 1, h->nbp);
+    return hipErrorInvalidValue;
 }
+
+const char *MPPI_CAT(mppi_mlp_name_a, MPPI_UNIT_A)(const mppi_handle *h, int src) { return pick_mlp<MPPI_UNIT_A>(h, src).name; }

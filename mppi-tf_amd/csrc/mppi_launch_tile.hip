@@ -5,23 +5,23 @@
 #error "compile with -DMPPI_UNIT_A=<action dimension 1..4> (mppi-tf_amd/build.py)"
 #endif
 
-// kernel dispatch
+struct TilePick {
+    decltype(&k_rollout_tile<MPPI_UNIT_A, 64, false, SRC_PHILOX, MODE_ROLLOUT>) kern; // nullptr: no instance serves (src, mode)
+    const char *name;
+};
+
 template <int A, int R, bool QFULL, int SRC, int MODE>
-static hipError_t launch_tile_inst(mppi_handle *h, hipStream_t st, const float *x_dev, const float *U_dev,
-                                   const float *eps, float *cost, float *part, float *noise_out)
+static TilePick tile_inst()
 {
-    auto kern = k_rollout_tile<A, R, QFULL, SRC, MODE>;
-    if (hipError_t e = mppi_raise_lds_ceiling(reinterpret_cast<const void *>(kern), h->device, h->tile_lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(h->nb), dim3(kThreads), h->tile_lds, st, h->dC, x_dev, U_dev, eps, h->d_step, cost, part, noise_out, 1, h->nbp);
-    return hipGetLastError();
+    static const std::string name = mppi_fmt("mppi::k_rollout_tile<%d, %d, %s, %d, %d>", A, R, mppi_tf(QFULL), SRC, MODE);
+    return {k_rollout_tile<A, R, QFULL, SRC, MODE>, name.c_str()};
 }
 
 template <int A, int R, bool QFULL>
-static hipError_t launch_tile_ar(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev,
-                                 const float *eps, float *cost, float *part, float *noise_out)
+static TilePick tile_mode(int src, int mode)
 {
 #define MPPI_TILE_CASE(SRC, MODE) \
-    if (src == SRC && mode == MODE) return launch_tile_inst<A, R, QFULL, SRC, MODE>(h, st, x_dev, U_dev, eps, cost, part, noise_out);
+    if (src == SRC && mode == MODE) return tile_inst<A, R, QFULL, SRC, MODE>();
     MPPI_TILE_CASE(SRC_PHILOX, MODE_ROLLOUT)
     MPPI_TILE_CASE(SRC_HBM, MODE_ROLLOUT)
     MPPI_TILE_CASE(SRC_PHILOX, MODE_COSTS_GIVEN)
@@ -30,25 +30,27 @@ static hipError_t launch_tile_ar(mppi_handle *h, hipStream_t st, int src, int mo
     MPPI_TILE_CASE(SRC_HBM, MODE_COST_ONLY)
     MPPI_TILE_CASE(SRC_PHILOX, MODE_NOISE_ONLY)
 #undef MPPI_TILE_CASE
-    return hipErrorInvalidValue;
+    return {nullptr, nullptr};
 }
 
-template <int A>
-static hipError_t launch_tile_a(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev,
-                                const float *eps, float *cost, float *part, float *noise_out)
+static TilePick pick_tile(const mppi_handle *h, int src, int mode)
 {
+    constexpr int A = MPPI_UNIT_A;
     const bool qf = h->hc.q_full != 0;
-#define MPPI_R_CASE(RR)                                                                                       \
-    if (h->R == RR) return qf ? launch_tile_ar<A, RR, true>(h, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out) \
-                              : launch_tile_ar<A, RR, false>(h, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
-    MPPI_R_CASE(64)
-    MPPI_R_CASE(32)
-    MPPI_R_CASE(16)
-#undef MPPI_R_CASE
-    return hipErrorInvalidValue;
+    if (h->R == 64) return qf ? tile_mode<A, 64, true>(src, mode) : tile_mode<A, 64, false>(src, mode);
+    if (h->R == 32) return qf ? tile_mode<A, 32, true>(src, mode) : tile_mode<A, 32, false>(src, mode);
+    if (h->R == 16) return qf ? tile_mode<A, 16, true>(src, mode) : tile_mode<A, 16, false>(src, mode);
+    return {nullptr, nullptr};
 }
 
-hipError_t MPPI_CAT(mppi_launch_tile_a, MPPI_UNIT_A)(MPPI_TILE_PARAMS)
+// (no kernel events: a profiled step records its events around this launch)
+hipError_t MPPI_CAT(mppi_tile_a, MPPI_UNIT_A)(MPPI_TILE_PARAMS)
 {
-    return launch_tile_a<MPPI_UNIT_A>(h, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
+    const TilePick p = pick_tile(h, src, mode);
+    if (!p.kern) return hipErrorInvalidValue;
+    if (hipError_t e = mppi_raise_lds_ceiling(reinterpret_cast<const void *>(p.kern), h->device, h->tile_lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(p.kern, dim3(h->nb), dim3(kThreads), h->tile_lds, st, h->dC, x_dev, U_dev, eps, h->d_step, cost, part, noise_out, 1, h->nbp);
+    return hipGetLastError();
 }
+
+const char *MPPI_CAT(mppi_tile_name_a, MPPI_UNIT_A)(const mppi_handle *h, int src, int mode) { return pick_tile(h, src, mode).name; }

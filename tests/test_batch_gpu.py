@@ -75,6 +75,8 @@ def test_batch_equals_standalone_handles(m, B, K, H, a, dense):
         for h in pair:
             h.set_action_sequence(U0[i])
         lone.append(pair)
+    # the batch runs the instance each member's lone handle runs on its two-launch path (k_rollout_pc<.., PASS = 0>), spelled in full
+    assert hb.rollout_kernel_name() == lone[0][1].rollout_kernel_name().replace("k_rollout_pc<", "k_rollout_pc_batch<")[:-len(", 0>")] + ">"
     if dense:
         lim = ([-0.3, -0.25][:a], [0.2, 0.35][:a])
         hb.set_action_limits(*lim)

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""A controller-parameter sweep as ONE batched controller: every point of a lambda x upsilon x gamma x noise grid is a member of one
+BatchHandle with its own lambda, upsilon, gamma and Sigma (BatchHandle's lams / upsilons / gammas / sigmas), and all of them step in the
+same two launches. This is the grid the reference sweeps with one process per point (5 x 4 x 5 x 3 = 300 runs of 300 steps):
+    python examples/sweep.py                                   # that grid, 300 steps, the point-mass static task
+    python examples/sweep.py --lams 0.05 0.2 --upsilons 1 2 --gammas 0.1 --noises 0.1 0.2 -s 5
+The controller uses the Python action-cost form (gamma, upsilon; ACTION_COST_PY) with upsilon scaling the noise (upsilon_scales_noise).
+Plant and controller are the point mass of examples/config/point_mass3d.yaml on the static task examples/config/static_task3d.yaml; noise
+n means Sigma = n I. Every member draws its noise from the same Philox key (--seed), as every run of the reference's sweep does. Prints the
+final distance to the goal of every grid point.
+The reference sweeps its ellipse task; a batch refuses the 2D ellipse cost (ElipseCost), so this sweep runs the static task."""
+import argparse
+import itertools
+import os
+import sys
+import time
+
+import numpy as np
+import yaml
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mppi_tf_amd as m  # noqa: E402
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def plant(X, U, dt, mass):
+    """the point mass, every member at once: x[2j] += dt v + dt^2/2 u/m, v += dt u/m (model_base.cpp:59-82, fp32)"""
+    X = X.copy()
+    a = U.shape[1]
+    bp, bq = np.float32(dt * dt / 2 / mass), np.float32(dt / mass)
+    for j in range(a):
+        X[:, 2 * j] = X[:, 2 * j] + np.float32(dt) * X[:, 2 * j + 1] + bp * U[:, j]
+        X[:, 2 * j + 1] = X[:, 2 * j + 1] + bq * U[:, j]
+    return X
+
+
+def main():
+    ap = argparse.ArgumentParser(description="lambda x upsilon x gamma x noise sweep as one batched controller")
+    ap.add_argument("--config", default=os.path.join(HERE, "config", "point_mass3d.yaml"))
+    ap.add_argument("--task", default=os.path.join(HERE, "config", "static_task3d.yaml"))
+    ap.add_argument("--lams", type=float, nargs="+", default=[0.05, 0.07, 0.1, 0.15, 0.2])
+    ap.add_argument("--upsilons", type=float, nargs="+", default=[1.0, 1.4, 1.8, 2.0])
+    ap.add_argument("--gammas", type=float, nargs="+", default=[0.05, 0.07, 0.1, 0.15, 0.2])
+    ap.add_argument("--noises", type=float, nargs="+", default=[0.10, 0.15, 0.20])
+    ap.add_argument("-s", "--steps", type=int, default=300)
+    ap.add_argument("--samples", type=int, default=None, help="samples per member (default: the config's)")
+    ap.add_argument("--seed", type=int, default=1)
+    o = ap.parse_args()
+    with open(o.config) as fh:
+        conf = yaml.safe_load(fh)
+    with open(o.task) as fh:
+        task = yaml.safe_load(fh)
+    s, a, dt, mass = conf["state-dim"], conf["action-dim"], float(conf["dt"]), float(conf["mass"])
+    goal = np.asarray(task["goal"], np.float32)
+    Q = np.asarray(task["Q"], np.float32)
+    if not task.get("diag", False):
+        Q = Q.reshape(s, s)
+    grid = list(itertools.product(o.lams, o.upsilons, o.gammas, o.noises))
+    n = len(grid)
+    hb = m.BatchHandle(n=n, k=o.samples or conf["samples"], tau=conf["horizon"], s_dim=s, a_dim=a, dt=dt, mass=mass, goal=goal, Q=Q,
+                       action_cost=m.ACTION_COST_PY, upsilon_scales_noise=True, seeds=[o.seed] * n,
+                       lams=[g[0] for g in grid], upsilons=[g[1] for g in grid], gammas=[g[2] for g in grid],
+                       sigmas=[g[3] * np.eye(a, dtype=np.float32) for g in grid])
+    X = np.zeros((n, s), np.float32)
+    t0 = time.perf_counter()
+    for _ in range(o.steps):
+        X = plant(X, hb.next(X), dt, mass)
+    wall = time.perf_counter() - t0
+    dist = np.linalg.norm(X[:, 0::2] - goal[0::2], axis=1)
+    print("%8s %8s %8s %8s  %s" % ("lambda", "upsilon", "gamma", "noise", "final goal distance"))
+    for (lam, ups, gam, noise), d in zip(grid, dist):
+        print("%8.3g %8.3g %8.3g %8.3g  %.4f" % (lam, ups, gam, noise, d))
+    best = int(np.argmin(dist))
+    print("%d grid points, %d steps in one batch: %.2f s (%.1f us per batched step); best: lambda %.3g upsilon %.3g gamma %.3g noise %.3g "
+          "(%.4f)" % (n, o.steps, wall, wall / max(o.steps, 1) * 1e6, *grid[best], dist[best]))
+    hb.close()
+
+
+if __name__ == "__main__":
+    main()

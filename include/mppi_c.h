@@ -403,10 +403,18 @@ mppi_status mppi_profile_end(mppi_handle *h, float *rollout_ms_avg, float *finis
 mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf, size_t n);
 
 /* ---- batched controllers: B independent MPPI problems stepped in the same two launches as one ------------------------------------
- * A batched handle holds n >= 1 members that share ONE mppi_config (k, tau, dt, mass, lambda, gamma, upsilon, sigma, Q, the action-cost
- * form, the action limits and the Philox step counter); each member has its own state, goal, action sequence (warm-started and shifted as
- * a lone handle's) and Philox key. Member m is bit for bit the handle mppi_create makes from the same config with cfg.seed = seeds[m], fed
- * the same x, goal and sequence on the same step counter: sample costs, U' and u. Members never interact.
+ * A batched handle holds n >= 1 members. mppi_create_batch_configs takes one mppi_config per member, cfgs[0..n):
+ *   per member: seed, goal, lambda, gamma, upsilon, sigma and Q (diagonal or dense), with its own state and action sequence (warm-started
+ *     and shifted as a lone handle's);
+ *   shared, and equal in every cfgs[m] (else MPPI_ERR_INVALID_ARG naming the field and the first member that differs): k, tau, dt, mass,
+ *     s_dim, a_dim, device, model_kind and the contents of auv, state_cost_kind and its parameters (quat_Q, ellipse3d), action_cost_kind,
+ *     flags, q_is_full, normalize_cost, shard_rank, shard_count; also the action limits and the Philox step counter.
+ * Every member must run the kernel instance member 0's lone handle runs: sigma diagonal for all members or dense for all, and Q diagonal
+ * for all or dense for all (a dense Q whose off-diagonal entries are all zero counts as diagonal, as in mppi_create); a mixed batch is
+ * MPPI_ERR_UNSUPPORTED naming sigma or Q. A singular sigma of member m is MPPI_ERR_SINGULAR_SIGMA naming m.
+ * Member m is bit for bit the handle mppi_create(&cfgs[m]) makes, fed the same x, goal and sequence on the same step counter: sample
+ * costs, beta, eta, U' and u. Members never interact. mppi_create_batch(cfg, n, seeds) is the batch of n copies of cfg with
+ * seed = seeds[m].
  * Serves
  *   - the point-mass model (a_dim 1..4) with the quadratic state cost (diagonal or dense Q), every horizon the producer/consumer rollout
  *     takes (tau <= 160; <= 132 above 512 tiles);
@@ -423,6 +431,8 @@ mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf, size_t n);
  * match, n < 1 and a member out of range are MPPI_ERR_INVALID_ARG. */
 /* n members; seeds[n] their Philox keys (NULL: cfg->seed + m); every goal starts as cfg->goal, every sequence as zeros */
 mppi_status mppi_create_batch(const mppi_config *cfg, int n, const uint64_t *seeds, mppi_handle **out);
+/* n members, member m from cfgs[m] (its seed, goal, lambda, gamma, upsilon, sigma, Q); every sequence starts as zeros */
+mppi_status mppi_create_batch_configs(const mppi_config *cfgs, int n, mppi_handle **out);
 /* the member count B; 0 for a plain handle */
 int mppi_batch_size(const mppi_handle *h);
 /* goals[B, s] (n = B*s_dim): every member's goal (setGoal per member) */
@@ -434,7 +444,8 @@ mppi_status mppi_batch_next_device(mppi_handle *h, const float *x_dev, float *u_
 /* every member's nominal sequence U[B, tau, a] (n = B*tau*a_dim); set resets the warm start as mppi_set_action_sequence does */
 mppi_status mppi_batch_get_action_sequences(mppi_handle *h, float *U, int n);
 mppi_status mppi_batch_set_action_sequences(mppi_handle *h, const float *U, int n);
-/* mppi_debug_get of ONE member (MPPI_DBG_*, the sizes of a lone handle); MPPI_DBG_NOISE regenerates the member's noise from seeds[member] */
+/* mppi_debug_get of ONE member (MPPI_DBG_*, the sizes of a lone handle) with the member's own constants: MPPI_DBG_WEIGHTS at its lambda,
+ * MPPI_DBG_NOISE regenerated from its Philox key and sigma */
 mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what, float *out, size_t n);
 
 /* ---- the learner of the learned model_base (replaces LearnerBase.train / _train_step, learners/learner_base.py:324-358,

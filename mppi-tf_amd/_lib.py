@@ -125,6 +125,7 @@ SIGNATURES = {
     "mppi_rollout_kernel_name": (C.c_int, [_H, C.c_char_p, C.c_size_t]),
     # batched controllers (BatchHandle)
     "mppi_create_batch": (C.c_int, [C.POINTER(Config), C.c_int, C.POINTER(C.c_uint64), C.POINTER(_H)]),
+    "mppi_create_batch_configs": (C.c_int, [C.POINTER(Config), C.c_int, C.POINTER(_H)]),
     "mppi_batch_size": (C.c_int, [_H]),
     "mppi_batch_set_goals": (C.c_int, [_H, FP, C.c_int]),
     "mppi_batch_next": (C.c_int, [_H, FP, C.c_int, FP, C.c_int]),
@@ -574,46 +575,90 @@ class Handle:
         return r.value, f.value, n.value
 
 
+def _batch_config(lib, keep, k, tau, s_dim, a_dim, dt, mass, lam, gamma, upsilon, sigma, goal, Q, q_is_full, action_cost, seed, device,
+                  upsilon_scales_noise, auv, quat_cost, ellipse3d):
+    """one mppi_config of a batch (BatchHandle's keywords); the arrays it points to are appended to `keep`"""
+    cfg = Config()
+    st = lib.mppi_config_init(C.byref(cfg), k, tau, dt, mass, s_dim, a_dim)
+    if st != OK:
+        raise MppiError(st, "%s (%s)" % ((lib.mppi_last_error(None) or b"").decode(), lib.mppi_status_string(st).decode()))
+    cfg.lam, cfg.gamma, cfg.upsilon, cfg.action_cost_kind = lam, gamma, upsilon, action_cost
+    cfg.seed, cfg.device, cfg.flags = seed, device, (1 if upsilon_scales_noise else 0)
+    Q = _fill_13state(cfg, keep, auv, quat_cost, ellipse3d, Q)
+    if sigma is not None:
+        keep.append(f32(sigma, (a_dim, a_dim)))
+        cfg.sigma = fp(keep[-1])
+    if goal is not None:
+        keep.append(f32(goal, (s_dim,)))
+        cfg.goal = fp(keep[-1])
+    if Q is not None:
+        q = f32(Q)
+        full = q.ndim == 2 if q_is_full is None else q_is_full
+        keep.append(f32(q, (s_dim, s_dim) if full else (s_dim,)))
+        cfg.Q, cfg.q_is_full = fp(keep[-1]), int(full)
+    return cfg
+
+
+# BatchHandle's per-member keywords: each replaces the shared keyword of the same name without the plural s
+BATCH_PER_MEMBER = {"lams": "lam", "gammas": "gamma", "upsilons": "upsilon", "sigmas": "sigma", "Qs": "Q"}
+
+
+def batch_configs(n, k, tau, s_dim, a_dim, dt=0.1, mass=1.0, lam=1.0, gamma=1.0, upsilon=1.0, sigma=None, goal=None, Q=None,
+                  q_is_full=None, action_cost=ACTION_COST_CPP, seed=1, seeds=None, device=0, upsilon_scales_noise=False, auv=None,
+                  quat_cost=False, ellipse3d=None, lams=None, gammas=None, upsilons=None, sigmas=None, Qs=None):
+    """-> (Config array [n] for mppi_create_batch_configs, objects that must outlive its use). Member m's config is the shared keywords'
+    with lam, gamma, upsilon, sigma and Q replaced by lams[m], gammas[m], upsilons[m], sigmas[m] ([a, a]) and Qs[m] ([s] or [s, s]) where
+    those are given, and seed = seeds[m] (None: seed + m, as mppi_create_batch). A list of the wrong length raises MppiError(ERR_INVALID_ARG)."""
+    lib = load()
+    per = dict(lams=lams, gammas=gammas, upsilons=upsilons, sigmas=sigmas, Qs=Qs, seeds=seeds)
+    for name, v in per.items():
+        if v is not None and len(v) != n:
+            raise MppiError(ERR_INVALID_ARG, "%s must hold n = %d entries, not %d" % (name, n, len(v)))
+    shared = dict(lam=lam, gamma=gamma, upsilon=upsilon, sigma=sigma, Q=Q)
+    cfgs, keep = (Config * n)(), []
+    for m in range(n):
+        own = {one: (shared[one] if per[many] is None else per[many][m]) for many, one in BATCH_PER_MEMBER.items()}
+        cfgs[m] = _batch_config(lib, keep, k, tau, s_dim, a_dim, dt, mass, own["lam"], own["gamma"], own["upsilon"], own["sigma"], goal,
+                                own["Q"], q_is_full, action_cost, int(seeds[m]) if seeds is not None else seed + m, device,
+                                upsilon_scales_noise, auv, quat_cost, ellipse3d)
+    return cfgs, keep
+
+
 class BatchHandle:
-    """RAII wrapper of a batched mppi_handle (mppi_create_batch): n independent controllers that share one configuration and step in the
-    same two launches. Member m is bit for bit Handle(..., seed=seeds[m]) fed the same x, goal and sequence (include/mppi_c.h)."""
+    """RAII wrapper of a batched mppi_handle (mppi_create_batch / mppi_create_batch_configs): n independent controllers that step in the
+    same two launches. Member m is bit for bit Handle(..., seed=seeds[m]) fed the same x, goal and sequence, with lams[m], gammas[m],
+    upsilons[m], sigmas[m] and Qs[m] where those are given (include/mppi_c.h)."""
 
     def __init__(self, n, k, tau, s_dim, a_dim, dt=0.1, mass=1.0, lam=1.0, gamma=1.0, upsilon=1.0, sigma=None, goal=None, goals=None,
                  Q=None, q_is_full=None, action_cost=ACTION_COST_CPP, seed=1, seeds=None, device=0, upsilon_scales_noise=False, tuning=None,
-                 auv=None, quat_cost=False, ellipse3d=None):
+                 auv=None, quat_cost=False, ellipse3d=None, lams=None, gammas=None, upsilons=None, sigmas=None, Qs=None):
         """n members; seeds: n Philox keys (None: seed + m); goal: every member's goal, goals: [n, s_dim] per member (after goal);
         the other keywords as Handle's. tuning: dict of diagnostic switches (keys of TUNING) that a batch takes.
         auv, quat_cost, ellipse3d: as Handle's (the Fossen AUV model, s_dim 13, a_dim 6; StaticQuatCost; ElipseCost3D); goals is then
-        [n, 13], next / next_device take x [n, 13] and give u [n, 6]."""
+        [n, 13], next / next_device take x [n, 13] and give u [n, 6].
+        lams, gammas, upsilons: n values; sigmas: [n, a_dim, a_dim]; Qs: [n, s_dim] or [n, s_dim, s_dim] — each member's own lambda, gamma,
+        upsilon, sigma and quadratic-cost Q (None: the shared keyword). Every member's sigma must be diagonal, or every one dense; so must Q."""
         lib = self.lib = load()
         self.h = _H()
-        cfg = Config()
-        self._check(lib.mppi_config_init(C.byref(cfg), k, tau, dt, mass, s_dim, a_dim), None)
-        cfg.lam, cfg.gamma, cfg.upsilon, cfg.action_cost_kind = lam, gamma, upsilon, action_cost
-        cfg.seed, cfg.device, cfg.flags = seed, device, (1 if upsilon_scales_noise else 0)
         keep = []
-        Q = _fill_13state(cfg, keep, auv, quat_cost, ellipse3d, Q)
-        if sigma is not None:
-            keep.append(f32(sigma, (a_dim, a_dim)))
-            cfg.sigma = fp(keep[-1])
-        if goal is not None:
-            keep.append(f32(goal, (s_dim,)))
-            cfg.goal = fp(keep[-1])
-        if Q is not None:
-            q = f32(Q)
-            if q_is_full is None:
-                q_is_full = q.ndim == 2
-            keep.append(f32(q, (s_dim, s_dim) if q_is_full else (s_dim,)))
-            cfg.Q, cfg.q_is_full = fp(keep[-1]), int(q_is_full)
-        sp = None
-        if seeds is not None:
-            sv = np.ascontiguousarray(seeds, np.uint64).ravel()
-            if sv.size != n:
-                raise MppiError(ERR_INVALID_ARG, "seeds must hold n values")
-            keep.append(sv)
-            sp = sv.ctypes.data_as(C.POINTER(C.c_uint64))
         self.n, self.k, self.tau, self.s, self.a = n, k, tau, s_dim, a_dim
-        st = lib.mppi_create_batch(C.byref(cfg), int(n), sp, C.byref(self.h))
+        if all(v is None for v in (lams, gammas, upsilons, sigmas, Qs)):
+            cfg = _batch_config(lib, keep, k, tau, s_dim, a_dim, dt, mass, lam, gamma, upsilon, sigma, goal, Q, q_is_full, action_cost, seed,
+                                device, upsilon_scales_noise, auv, quat_cost, ellipse3d)
+            sp = None
+            if seeds is not None:
+                sv = np.ascontiguousarray(seeds, np.uint64).ravel()
+                if sv.size != n:
+                    raise MppiError(ERR_INVALID_ARG, "seeds must hold n values")
+                keep.append(sv)
+                sp = sv.ctypes.data_as(C.POINTER(C.c_uint64))
+            st = lib.mppi_create_batch(C.byref(cfg), int(n), sp, C.byref(self.h))
+        else:
+            cfgs, keep = batch_configs(n, k, tau, s_dim, a_dim, dt=dt, mass=mass, lam=lam, gamma=gamma, upsilon=upsilon, sigma=sigma,
+                                       goal=goal, Q=Q, q_is_full=q_is_full, action_cost=action_cost, seed=seed, seeds=seeds, device=device,
+                                       upsilon_scales_noise=upsilon_scales_noise, auv=auv, quat_cost=quat_cost, ellipse3d=ellipse3d,
+                                       lams=lams, gammas=gammas, upsilons=upsilons, sigmas=sigmas, Qs=Qs)
+            st = lib.mppi_create_batch_configs(cfgs, int(n), C.byref(self.h))
         if st != OK:
             self.h = _H()
             self._check(st, None)

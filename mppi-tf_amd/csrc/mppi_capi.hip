@@ -6,6 +6,7 @@
 #include <chrono>
 #include <dlfcn.h>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -236,8 +237,7 @@ extern "C" void mppi_destroy(mppi_handle *h)
                      h->d_record, h->d_dbg, h->d_mm, h->d_eps, h->d_recs, h->d_range, h->d_tile_mm};
     for (float *p : bufs) if (p) (void)hipFree(p);
     if (h->d_step) (void)hipFree(h->d_step);
-    if (h->d_seeds) (void)hipFree(h->d_seeds);
-    for (float *p : {h->d_goals, h->d_bx, h->d_bu}) if (p) (void)hipFree(p);
+    for (float *p : {h->d_bx, h->d_bu}) if (p) (void)hipFree(p);
     if (h->dM) (void)hipFree(h->dM);
     if (h->d_mlp_w) (void)hipFree(h->d_mlp_w);
     if (h->dC) (void)hipFree(h->dC);
@@ -302,6 +302,54 @@ static mppi_status upload_mlp(mppi_handle *h, const mppi_mlp_desc *d, bool alloc
     HIP_TRY(h, hipMemcpyAsync(h->dM, &h->hm, sizeof(MlpDev), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MPPI_OK;
+}
+
+// The constants of one controller from its config, on the geometry mppi_create derived (K_local, k_offset, H, s, a): mppi_create's, and
+// once per member in mppi_create_batch_configs. sigma_diag: 1 when Σ and Σ⁻¹ are diagonal (the DIAG instances). false: Σ is singular.
+static bool fill_consts(const mppi_config *cfg, const mppi_handle *h, DevConsts &c, int &sigma_diag)
+{
+    const int s = h->s, a = h->a;
+    c.K_local = h->K_local; c.k_offset = h->k_offset; c.H = h->H; c.s = s; c.a = a;
+    c.q_full = cfg->q_is_full ? 1 : 0;
+    c.action_cost_kind = cfg->action_cost_kind; c.model_kind = cfg->model_kind;
+    c.state_cost_kind = cfg->state_cost_kind;
+    if (cfg->state_cost_kind == MPPI_STATE_COST_ELLIPSE) for (int i = 0; i < 7; ++i) c.ell[i] = cfg->ellipse[i];
+    c.lambda = cfg->lambda; c.neg_inv_lambda = -1.0f / cfg->lambda;
+    c.gamma = cfg->gamma; c.upsilon = cfg->upsilon;
+    c.py_ncoef = cfg->lambda * (1.0f - 1.0f / cfg->upsilon);
+    c.dt = cfg->dt;
+    c.bp = ((cfg->dt * cfg->dt) / 2.0f) / cfg->mass; // model_base.cpp:72 then RealDiv :74-76
+    c.bq = cfg->dt / cfg->mass;
+    c.seed = cfg->seed;
+    for (int i = 0; i < s; ++i) c.goal[i] = cfg->goal ? cfg->goal[i] : ((i & 1) ? 0.0f : 1.0f);
+    float sig[kMaxA * kMaxA], inv[kMaxA * kMaxA];
+    for (int i = 0; i < a; ++i) for (int j = 0; j < a; ++j) sig[i * a + j] = cfg->sigma ? cfg->sigma[i * a + j] : (i == j ? 1.0f : 0.0f);
+    if (!invert(sig, a, inv)) return false;
+    sigma_diag = 1;
+    // the sampler's matrix: Σ (C++, controller_base.cpp:201) or υ·Σ (Py build_noise); Σ⁻¹ stays that of Σ
+    const float samp = (cfg->flags & MPPI_FLAG_UPSILON_SCALES_NOISE) ? cfg->upsilon : 1.0f;
+    for (int i = 0; i < a; ++i) for (int j = 0; j < a; ++j) {
+        c.sigma[i * kMaxA + j] = samp * sig[i * a + j]; c.sigma_inv[i * kMaxA + j] = inv[i * a + j];
+        if (i != j && (sig[i * a + j] != 0.0f || inv[i * a + j] != 0.0f)) sigma_diag = 0;
+    }
+    bool q_offdiag = false;
+    for (int i = 0; i < s; ++i) {
+        if (cfg->q_is_full) {
+            for (int j = 0; j < s; ++j) {
+                c.qfull[i * kMaxS + j] = cfg->Q ? cfg->Q[i * s + j] : (i == j ? 1.0f : 0.0f);
+                if (i != j && c.qfull[i * kMaxS + j] != 0.0f) q_offdiag = true;
+            }
+            c.qdiag[i] = c.qfull[i * kMaxS + i];
+        } else {
+            c.qdiag[i] = cfg->Q ? cfg->Q[i] : 1.0f;
+            c.qfull[i * kMaxS + i] = c.qdiag[i];
+        }
+    }
+
+    // A dense Q whose off-diagonal entries are all exactly zero (the Python reference's default task files)
+    // evaluates bit-identically through the diagonal instances: the dropped products are exact zeros.
+    if (cfg->q_is_full && !q_offdiag) c.q_full = 0;
+    return true;
 }
 
 extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
@@ -384,47 +432,7 @@ extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
     // >= 4 tiles share a CU (the kernel is VALU-issue bound there): pick by tiles per CU.
     h->pc_np = ((h->K_local + 63) / 64 <= 2 * 256) ? 5 : 3;
 
-    DevConsts &c = h->hc;
-    c.K_local = h->K_local; c.k_offset = h->k_offset; c.H = h->H; c.s = s; c.a = a;
-    c.q_full = cfg->q_is_full ? 1 : 0;
-    c.action_cost_kind = cfg->action_cost_kind; c.model_kind = cfg->model_kind;
-    c.state_cost_kind = cfg->state_cost_kind;
-    if (cfg->state_cost_kind == MPPI_STATE_COST_ELLIPSE) for (int i = 0; i < 7; ++i) c.ell[i] = cfg->ellipse[i];
-    c.lambda = cfg->lambda; c.neg_inv_lambda = -1.0f / cfg->lambda;
-    c.gamma = cfg->gamma; c.upsilon = cfg->upsilon;
-    c.py_ncoef = cfg->lambda * (1.0f - 1.0f / cfg->upsilon);
-    c.dt = cfg->dt;
-    c.bp = ((cfg->dt * cfg->dt) / 2.0f) / cfg->mass; // model_base.cpp:72 then RealDiv :74-76
-    c.bq = cfg->dt / cfg->mass;
-    c.seed = cfg->seed;
-    for (int i = 0; i < s; ++i) c.goal[i] = cfg->goal ? cfg->goal[i] : ((i & 1) ? 0.0f : 1.0f);
-    float sig[kMaxA * kMaxA], inv[kMaxA * kMaxA];
-    for (int i = 0; i < a; ++i) for (int j = 0; j < a; ++j) sig[i * a + j] = cfg->sigma ? cfg->sigma[i * a + j] : (i == j ? 1.0f : 0.0f);
-    if (!invert(sig, a, inv)) { delete h; return fail(nullptr, MPPI_ERR_SINGULAR_SIGMA, "sigma is singular"); }
-    h->sigma_diag = 1;
-    // the sampler's matrix: Σ (C++, controller_base.cpp:201) or υ·Σ (Py build_noise); Σ⁻¹ stays that of Σ
-    const float samp = (cfg->flags & MPPI_FLAG_UPSILON_SCALES_NOISE) ? cfg->upsilon : 1.0f;
-    for (int i = 0; i < a; ++i) for (int j = 0; j < a; ++j) {
-        c.sigma[i * kMaxA + j] = samp * sig[i * a + j]; c.sigma_inv[i * kMaxA + j] = inv[i * a + j];
-        if (i != j && (sig[i * a + j] != 0.0f || inv[i * a + j] != 0.0f)) h->sigma_diag = 0;
-    }
-    bool q_offdiag = false;
-    for (int i = 0; i < s; ++i) {
-        if (cfg->q_is_full) {
-            for (int j = 0; j < s; ++j) {
-                c.qfull[i * kMaxS + j] = cfg->Q ? cfg->Q[i * s + j] : (i == j ? 1.0f : 0.0f);
-                if (i != j && c.qfull[i * kMaxS + j] != 0.0f) q_offdiag = true;
-            }
-            c.qdiag[i] = c.qfull[i * kMaxS + i];
-        } else {
-            c.qdiag[i] = cfg->Q ? cfg->Q[i] : 1.0f;
-            c.qfull[i * kMaxS + i] = c.qdiag[i];
-        }
-    }
-
-    // A dense Q whose off-diagonal entries are all exactly zero (the Python reference's default task files)
-    // evaluates bit-identically through the diagonal instances: the dropped products are exact zeros.
-    if (cfg->q_is_full && !q_offdiag) c.q_full = 0;
+    if (!fill_consts(cfg, h, h->hc, h->sigma_diag)) { delete h; return fail(nullptr, MPPI_ERR_SINGULAR_SIGMA, "sigma is singular"); }
 
     // tile geometry: the largest R in {64,32,16} whose LDS image fits one CU (160 KiB), preferring
     // <= ~53 KiB so three workgroups share a CU.
@@ -1896,9 +1904,10 @@ extern "C" mppi_status mppi_shift(const float *U, int tau, int a, const float *i
     return MPPI_OK;
 }
 
-// ---- batched controllers (mppi_create_batch; kernels in mppi_launch_batch.hip and mppi_launch_batch_gen.hip) -----------------------
-// B members share one mppi_config; each has its own x, goal, sequence and Philox key. Member m is bit for bit the lone handle made from the
-// same config with cfg.seed = seeds[m], fed the same x, goal and sequence, on the same step counter: the batched rollout is the text of
+// ---- batched controllers (mppi_create_batch_configs; kernels in mppi_launch_batch.hip and mppi_launch_batch_gen.hip) ---------------
+// Member m is made from cfgs[m]: its own seed, goal, lambda, gamma, upsilon, sigma and Q (its DevConsts block dC + m), its own x and
+// sequence; the rest of the config is shared. Member m is bit for bit the lone handle mppi_create(&cfgs[m]), fed the same x, goal and
+// sequence, on the same step counter: the batched rollout is the text of
 // k_rollout_pc (the point mass) or k_rollout_auv_pc (the Fossen AUV model) with per-member operands, with the instance that handle would
 // launch, and the batched finish is k_finish_cols' column_combine on the member's records over the same padded record count.
 // the Fossen AUV model on its two-wave rollout (k_rollout_auv_pc, every horizon) with the step's one pass: what k_rollout_auv_pc_batch runs
@@ -1939,27 +1948,95 @@ static const char *batch_refusal(const mppi_config *cfg)
     return nullptr;
 }
 
-extern "C" mppi_status mppi_create_batch(const mppi_config *cfg, int n, const uint64_t *seeds, mppi_handle **out)
+static bool same_bits(float x, float y) { return std::memcmp(&x, &y, sizeof(float)) == 0; }
+static bool same_floats(const float *x, const float *y, int n) // NULL = zeros
 {
-    if (!cfg || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfg/out is NULL");
-    *out = nullptr;
-    if (n < 1) return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: n must be >= 1");
-    if (cfg->struct_size != sizeof(mppi_config)) return fail(nullptr, MPPI_ERR_INVALID_ARG, "mppi_config.struct_size mismatch (use mppi_config_init)");
+    for (int i = 0; i < n; ++i) if (!same_bits(x ? x[i] : 0.0f, y ? y[i] : 0.0f)) return false;
+    return true;
+}
+static bool same_auv(const mppi_auv_desc *x, const mppi_auv_desc *y)
+{
+    if (!x || !y) return x == y;
+    return same_bits(x->mass, y->mass) && same_bits(x->volume, y->volume) && same_bits(x->density, y->density) &&
+           same_bits(x->gravity, y->gravity) && same_floats(x->cog, y->cog, 3) && same_floats(x->cob, y->cob, 3) &&
+           same_floats(x->inertial, y->inertial, 6) && same_floats(x->added_mass, y->added_mass, 36) &&
+           same_floats(x->linear_damping, y->linear_damping, 36) &&
+           same_floats(x->linear_damping_forward_speed, y->linear_damping_forward_speed, 36) &&
+           same_floats(x->quad_damping, y->quad_damping, 6) && x->rk == y->rk;
+}
+
+// The first field that every member must share in which b differs from a (NULL: none). What mppi_create derives the geometry, the model,
+// the cost's form and the kernel picks from is shared; seed, goal, lambda, gamma, upsilon, sigma and Q are each member's own.
+static const char *batch_shared_diff(const mppi_config *a, const mppi_config *b)
+{
+    if (a->k != b->k) return "k";
+    if (a->tau != b->tau) return "tau";
+    if (!same_bits(a->dt, b->dt)) return "dt";
+    if (!same_bits(a->mass, b->mass)) return "mass";
+    if (a->s_dim != b->s_dim) return "s_dim";
+    if (a->a_dim != b->a_dim) return "a_dim";
+    if (a->device != b->device) return "device";
+    if (a->model_kind != b->model_kind) return "model_kind";
+    if (a->model_kind == MPPI_MODEL_AUV && !same_auv(a->auv, b->auv)) return "auv";
+    if (a->state_cost_kind != b->state_cost_kind) return "state_cost_kind";
+    if (a->state_cost_kind == MPPI_STATE_COST_QUAT && !same_floats(a->quat_Q, b->quat_Q, 100)) return "quat_Q";
+    if (a->state_cost_kind == MPPI_STATE_COST_ELLIPSE3D && !same_floats(a->ellipse3d, b->ellipse3d, 11)) return "ellipse3d";
+    if (a->action_cost_kind != b->action_cost_kind) return "action_cost_kind";
+    if (a->flags != b->flags) return "flags";
+    if (a->q_is_full != b->q_is_full) return "q_is_full";
+    if (a->normalize_cost != b->normalize_cost) return "normalize_cost";
+    if (a->shard_rank != b->shard_rank) return "shard_rank";
+    if (a->shard_count != b->shard_count) return "shard_count";
+    return nullptr;
+}
+
+// The batch of n members cfgs[0..n) (n >= 1). The handle is mppi_create(&cfgs[0])'s with B-fold per-member buffers, and B DevConsts blocks,
+// member m's filled from cfgs[m] exactly as mppi_create fills a lone handle's. name_members: prefix what mppi_create reports for cfgs[0]
+// with the member (mppi_create_batch_configs); mppi_create_batch keeps the messages it always gave.
+static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_members, mppi_handle **out)
+{
+    for (int m = 0; m < n; ++m)
+        if (cfgs[m].struct_size != sizeof(mppi_config)) return fail(nullptr, MPPI_ERR_INVALID_ARG, "mppi_config.struct_size mismatch (use mppi_config_init)");
+    for (int m = 1; m < n; ++m)
+        if (const char *f = batch_shared_diff(&cfgs[0], &cfgs[m]))
+            return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: cfgs[" + std::to_string(m) + "]." + f + " differs from cfgs[0]." + f + " (every member shares it)");
+    const mppi_config *cfg = &cfgs[0];
     if (const char *why = batch_refusal(cfg)) return fail(nullptr, MPPI_ERR_UNSUPPORTED, why);
     mppi_handle *h = nullptr;
-    if (mppi_status st = mppi_create(cfg, &h); st != MPPI_OK) return st;
+    if (mppi_status st = mppi_create(cfg, &h); st != MPPI_OK) {
+        if (name_members) return fail(nullptr, st, "batched controllers: member 0: " + g_create_err);
+        return st;
+    }
     auto refuse = [&](mppi_status st, const std::string &why) { mppi_destroy(h); return fail(nullptr, st, why); };
     if (!h->is_gen && !pc_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: the producer/consumer rollout serves this shape only with s_dim = 2 a_dim, a_dim <= 4, tau <= 160 (<= 132 above 512 tiles)");
     if (h->is_gen && !auv_batch_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: the Fossen AUV model is batched on its two-wave rollout (k_rollout_auv_pc) only");
     if (h->nbp > 1024) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: at most 1024 tiles (k = 65536) per member (the finish combines a member's records in one pass)");
     if ((long long)h->nb * n > (1ll << 30) / 64) return refuse(MPPI_ERR_INVALID_ARG, "batched controllers: n * k too large");
     const int B = n, s = h->s, a = h->a, HA = h->HA;
+    // every member's constants; all members must run the instance member 0's lone handle picks (sigma_diag, the effective Q form)
+    std::vector<DevConsts> consts(B);
+    consts[0] = h->hc;
+    for (int m = 1; m < B; ++m) {
+        if (!(cfgs[m].lambda > 0.0f) || !(cfgs[m].upsilon != 0.0f))
+            return refuse(MPPI_ERR_INVALID_ARG, "batched controllers: member " + std::to_string(m) + ": lambda must be > 0, upsilon != 0");
+        int diag = 0;
+        if (!fill_consts(&cfgs[m], h, consts[m], diag)) return refuse(MPPI_ERR_SINGULAR_SIGMA, "batched controllers: member " + std::to_string(m) + ": sigma is singular");
+        if (diag != h->sigma_diag)
+            return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: sigma must be diagonal for every member or dense for every member (member " + std::to_string(m) + " differs from member 0)");
+        if (consts[m].q_full != h->hc.q_full)
+            return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: Q must be diagonal for every member or dense for every member (member " + std::to_string(m) +
+                                                    " differs from member 0; a dense Q without off-diagonal entries counts as diagonal)");
+    }
     const size_t K = (size_t)h->K_local, rec = (size_t)h->nbp * (2 + HA), us = (size_t)HA + a;
     auto body = [&]() -> mppi_status {
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         // the per-member buffers replace the single controller's (same names, B times the size)
         for (float **p : {&h->d_Ubuf[0], &h->d_Ubuf[1], &h->d_cost, &h->d_part, &h->d_dbg}) { HIP_TRY(h, hipFree(*p)); *p = nullptr; }
+        HIP_TRY(h, hipFree(h->dC));
+        h->dC = nullptr;
+        HIP_TRY(h, hipMalloc((void **)&h->dC, sizeof(DevConsts) * B));
+        HIP_TRY(h, hipMemcpyAsync(h->dC, consts.data(), sizeof(DevConsts) * B, hipMemcpyHostToDevice, h->stream));
         for (int i = 0; i < 2; ++i) {
             HIP_TRY(h, hipMalloc((void **)&h->d_Ubuf[i], sizeof(float) * us * B));
             HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, sizeof(float) * us * B, h->stream)); // U0 = 0, zero tails
@@ -1974,14 +2051,6 @@ extern "C" mppi_status mppi_create_batch(const mppi_config *cfg, int n, const ui
             hipLaunchKernelGGL(k_fill_records, dim3((unsigned)((rec + 255) / 256)), dim3(256), 0, h->stream, h->d_part + rec * m, h->nbp, 2 + HA);
         HIP_TRY(h, hipGetLastError());
         h->part_nb = h->nb;
-        h->seeds.resize(B);
-        for (int m = 0; m < B; ++m) h->seeds[m] = seeds ? seeds[m] : cfg->seed + (unsigned long long)m;
-        HIP_TRY(h, hipMalloc((void **)&h->d_seeds, sizeof(unsigned long long) * B));
-        HIP_TRY(h, hipMemcpyAsync(h->d_seeds, h->seeds.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice, h->stream));
-        std::vector<float> goals((size_t)B * s);
-        for (int m = 0; m < B; ++m) for (int i = 0; i < s; ++i) goals[(size_t)m * s + i] = h->hc.goal[i];
-        HIP_TRY(h, hipMalloc((void **)&h->d_goals, sizeof(float) * goals.size()));
-        HIP_TRY(h, hipMemcpyAsync(h->d_goals, goals.data(), sizeof(float) * goals.size(), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipMalloc((void **)&h->d_bx, sizeof(float) * (size_t)B * s));
         HIP_TRY(h, hipMalloc((void **)&h->d_bu, sizeof(float) * (size_t)B * a));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1992,6 +2061,31 @@ extern "C" mppi_status mppi_create_batch(const mppi_config *cfg, int n, const ui
     if (mppi_status st = body(); st != MPPI_OK) { g_create_err = h->err; mppi_destroy(h); return st; }
     *out = h;
     return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_create_batch_configs(const mppi_config *cfgs, int n, mppi_handle **out)
+{
+    if (!cfgs || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfgs/out is NULL");
+    *out = nullptr;
+    if (n < 1) return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: n must be >= 1");
+    return create_batch(cfgs, n, true, out);
+}
+
+// n copies of cfg that differ in the seed
+extern "C" mppi_status mppi_create_batch(const mppi_config *cfg, int n, const uint64_t *seeds, mppi_handle **out)
+{
+    if (!cfg || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfg/out is NULL");
+    *out = nullptr;
+    if (n < 1) return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: n must be >= 1");
+    if (cfg->struct_size != sizeof(mppi_config)) return fail(nullptr, MPPI_ERR_INVALID_ARG, "mppi_config.struct_size mismatch (use mppi_config_init)");
+    std::vector<mppi_config> cfgs;
+    try {
+        cfgs.assign((size_t)n, *cfg);
+    } catch (const std::bad_alloc &) {
+        return fail(nullptr, MPPI_ERR_ALLOC, "out of host memory");
+    }
+    for (int m = 0; m < n; ++m) cfgs[m].seed = seeds ? seeds[m] : cfg->seed + (unsigned long long)m;
+    return create_batch(cfgs.data(), n, false, out);
 }
 
 extern "C" int mppi_batch_size(const mppi_handle *h) { return h ? h->batch : 0; }
@@ -2027,8 +2121,11 @@ extern "C" mppi_status mppi_batch_set_goals(mppi_handle *h, const float *goals, 
     MPPI_BATCH_ONLY(h);
     if (!goals || n != h->batch * h->s) return fail(h, MPPI_ERR_INVALID_ARG, "goals must hold n * s_dim floats");
     MPPI_ENTER(h);
-    HIP_TRY(h, hipMemcpyAsync(h->d_goals, goals, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    // into each member's constants (dC + m), the one copy the kernels read; hc mirrors member 0's
+    const size_t row = sizeof(float) * h->s;
+    HIP_TRY(h, hipMemcpy2DAsync((char *)h->dC + offsetof(DevConsts, goal), sizeof(DevConsts), goals, row, row, h->batch, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < h->s; ++i) h->hc.goal[i] = goals[i];
     return MPPI_OK;
 }
 
@@ -2099,14 +2196,14 @@ extern "C" mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what
         need = K;
         if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
         HIP_TRY(h, hipMalloc((void **)&tmp, sizeof(float) * K));
-        hipLaunchKernelGGL(k_weights, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, (const DevConsts *)h->dC, (const float *)(h->d_cost + K * member),
+        hipLaunchKernelGGL(k_weights, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, (const DevConsts *)(h->dC + member), (const float *)(h->d_cost + K * member),
                            (int)K, (const float *)dbg, (float *)nullptr, (float *)nullptr, tmp, (const float *)nullptr);
         src = tmp;
         break;
     }
     case MPPI_DBG_NOISE: {
-        // the member's noise of the LAST step, regenerated from its Philox key at the previous step counter by the noise-only pass of the
-        // tile kernel (the point mass) or of k_rollout_gen (the AUV), as mppi_debug_get; the constants carry the member's key for that launch
+        // the member's noise of the LAST step, regenerated from its Philox key and Sigma at the previous step counter by the noise-only pass of
+        // the tile kernel (the point mass) or of k_rollout_gen (the AUV), as mppi_debug_get; that launch reads the member's constants (dC + m)
         need = K * (size_t)h->HA;
         if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
         if (mppi_status s = ensure_eps(h); s != MPPI_OK) return s;
@@ -2114,19 +2211,15 @@ extern "C" mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what
         HIP_TRY(h, hipMemcpyAsync(&cur, h->d_step, sizeof(cur), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (cur == 0) return fail(h, MPPI_ERR_INVALID_ARG, "no step has run yet");
-        const unsigned long long prev = cur - 1, own_seed = h->hc.seed;
-        h->hc.seed = h->seeds[member];
-        mppi_status us = upload_consts(h);
-        if (us == MPPI_OK) {
-            HIP_TRY(h, hipMemcpyAsync(h->d_step, &prev, sizeof(prev), hipMemcpyHostToDevice, h->stream));
-            const hipError_t le = h->is_gen ? mppi_launch_gen(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps)
-                                            : launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
-            HIP_TRY(h, hipMemcpyAsync(h->d_step, &cur, sizeof(cur), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, le);
-        }
-        h->hc.seed = own_seed;
-        if (mppi_status s2 = upload_consts(h); us == MPPI_OK) us = s2;
-        if (us != MPPI_OK) return us;
+        const unsigned long long prev = cur - 1;
+        HIP_TRY(h, hipMemcpyAsync(h->d_step, &prev, sizeof(prev), hipMemcpyHostToDevice, h->stream));
+        DevConsts *const own = h->dC;
+        h->dC = own + member;
+        const hipError_t le = h->is_gen ? mppi_launch_gen(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps)
+                                        : launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
+        h->dC = own;
+        HIP_TRY(h, hipMemcpyAsync(h->d_step, &cur, sizeof(cur), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, le);
         src = h->d_eps;
         break;
     }

@@ -325,9 +325,8 @@ __device__ __forceinline__ void auv_step(const GT *__restrict__ G, float (&x)[kG
 }
 
 // ---------------------------------------------------------------------------------------- costs
-// static_cost.py:141-159 dist + :114-139 state_cost. GT: where the goal is read (C->goal): DevConsts, or a batch member's GenGoalRef
-template <class GT = DevConsts>
-__device__ __forceinline__ float state_cost_quat(const GT *__restrict__ C, const GenConsts *__restrict__ G, const float (&x)[kGenS])
+// static_cost.py:141-159 dist + :114-139 state_cost
+__device__ __forceinline__ float state_cost_quat(const DevConsts *__restrict__ C, const GenConsts *__restrict__ G, const float (&x)[kGenS])
 {
     float d[10], left[10];
     float dot = x[3] * C->goal[3];
@@ -446,20 +445,6 @@ __device__ __forceinline__ float gen_state_cost(const DevConsts *__restrict__ C,
     if (C->state_cost_kind == MPPI_STATE_COST_ELLIPSE3D) return state_cost_e3(G, x);
     if (C->q_full) return state_cost<kGenS, true>(C, x);
     return state_cost<kGenS, false>(C, x);
-}
-
-// The goal of one member of a batched handle (k_rollout_auv_pc_batch): the costs that read C->goal directly in gen_state_cost read it here,
-// with the shared dense Q; same operations in the same order
-struct GenGoalRef {
-    const float *goal;  // [kGenS]
-    const float *qfull; // DevConsts::qfull, [kGenS][kMaxS]
-};
-__device__ __forceinline__ float gen_state_cost_goal(const DevConsts *__restrict__ C, const GenConsts *__restrict__ G, const GenGoalRef *__restrict__ g,
-                                                     const float (&x)[kGenS])
-{
-    if (C->state_cost_kind == MPPI_STATE_COST_QUAT) return state_cost_quat(g, G, x);
-    if (C->state_cost_kind == MPPI_STATE_COST_ELLIPSE3D) return state_cost_e3(G, x);
-    return state_cost<kGenS, true>(g, x); // (the diagonal quadratic cost runs on the kernel's own GenQuadConsts)
 }
 
 // ---------------------------------------------------------------------------------------- NNAUVModel on the vector ALU
@@ -1541,11 +1526,12 @@ __global__ __launch_bounds__(kAuvPcThreads, 2) void k_rollout_auv_pc(
 #undef MPPI_AUV_BATCH
 }
 
-// k_rollout_auv_pc_batch: B Fossen AUV controllers that share one DevConsts and GenConsts (vehicle, rk, dt, Sigma, lambda, Q, the cost) in ONE
-// flat grid of B * W workgroups, W = (n_tiles + 1) / 2 per member. Workgroup w serves member m = w / W, tiles 2 (w - m W) + pair of it;
-// n_tiles is the member's tile count (a ragged K leaves the last workgroup of EVERY member with one tile). Member m reads x at x_dev + 13m,
-// U at U_dev + m * bt.u_stride, the key bt.seeds[m] (the noise and the record's regenerated noise), the goal bt.goals + 13m; it writes
-// its costs at cost + m K and its records at partials + m * bt.rec_stride ([2 + H*6][rsc] column-major, as the lone launch). The kernel
+// k_rollout_auv_pc_batch: B Fossen AUV controllers that share one GenConsts (vehicle, rk, dt, the StaticQuatCost / ElipseCost3D parameters)
+// in ONE flat grid of B * W workgroups, W = (n_tiles + 1) / 2 per member. Workgroup w serves member m = w / W, tiles 2 (w - m W) + pair of
+// it; n_tiles is the member's tile count (a ragged K leaves the last workgroup of EVERY member with one tile). Member m reads x at
+// x_dev + 13m, U at U_dev + m * bt.u_stride and its constants at C + m (the key and Sigma of the noise and of the record's regenerated
+// noise, lambda, the goal, Q); it writes its costs at cost + m K and its records at partials + m * bt.rec_stride ([2 + H*6][rsc]
+// column-major, as the lone launch). The kernel
 // waits at its own workgroup barriers only (no flag, counter or spin across workgroups): any B is free of deadlock, resident in one round
 // of the chip or not. Rollouts from Philox noise only (SRC_PHILOX, MODE_ROLLOUT): the step of a batched handle.
 template <bool DIAG>

@@ -127,14 +127,13 @@ struct mppi_handle {
     unsigned long long pre_step = 0; // host mirror of the Philox step counter
     unsigned long long pre_count = 0; // launches since the mode was entered (parity = stream)
     unsigned next_seq() { step_seq = (step_seq + 1u) & 0x7fffffffu; if (step_seq == 0u) step_seq = 1u; return step_seq; }
-    // a batched handle (mppi_create_batch): `batch` controllers sharing this configuration, stepped together (mppi_launch_batch.hip; the
-    // Fossen AUV model: mppi_launch_batch_gen.hip).
+    // a batched handle (mppi_create_batch_configs): `batch` controllers sharing this geometry, stepped together (mppi_launch_batch.hip; the
+    // Fossen AUV model: mppi_launch_batch_gen.hip). hc is member 0's constants.
     // Per member m: x at d_bx + m*s, U in d_Ubuf[i] + m*(HA + a) (each with its zero tail), costs at d_cost + m*K, records at
-    // d_part + m*nbp*(2 + HA), beta/eta at d_dbg + 8m, Philox key d_seeds[m], goal d_goals + m*s. 0 = a plain handle.
+    // d_part + m*nbp*(2 + HA), beta/eta at d_dbg + 8m, constants (Philox key, goal, lambda, gamma, upsilon, Sigma, Q) at dC + m.
+    // 0 = a plain handle.
     int batch = 0;
-    std::vector<unsigned long long> seeds;
-    unsigned long long *d_seeds = nullptr;
-    float *d_goals = nullptr, *d_bx = nullptr, *d_bu = nullptr;
+    float *d_bx = nullptr, *d_bu = nullptr;
     size_t xchg_step_slots() const { return (size_t)2 * HA * shard_count * 3; }
     size_t xchg_inbox_bytes() const { return sizeof(unsigned long long) * (xchg_step_slots() + (size_t)2 * shard_count); }
 };

@@ -222,12 +222,11 @@ enum { PC_COST_DIAG = 0, PC_COST_ELLIPSE = 1, PC_COST_DENSE = 2, PC_COST_DIAG_FM
 //                       mm_out[2] (a K-sharded handle, whose range the ranks agreed on). Replaces a full second rollout pass and the
 //                       single-workgroup k_cost_minmax launch between the two (42 -> 33 us per normalised step at configs[2]'s shape).
 enum { PC_PASS_PLAIN = 0, PC_PASS_COSTS = 1, PC_PASS_WEIGHTS = 2 };
-// A batched launch (k_rollout_pc_batch below, mppi_launch_batch.hip): B independent controllers that share one DevConsts, in ONE flat grid
-// of B * nb tiles. Workgroup w serves member m = w / nb, local tile b = w - m * nb; each member has its own x, U, goal, Philox key, costs
-// and record block. The grid stays 1-D so that the role placement and the generations' head starts (blockIdx.x >> 8) see the whole grid.
+// A batched launch (k_rollout_pc_batch below, mppi_launch_batch.hip): B independent controllers in ONE flat grid of B * nb tiles. Workgroup
+// w serves member m = w / nb, local tile b = w - m * nb; each member has its own x, U, costs, record block and DevConsts block C[m] (Philox
+// key, goal, lambda, gamma, upsilon, Sigma, Q: what mppi_create fills from the member's config; the geometry is the same in every block).
+// The grid stays 1-D so that the role placement and the generations' head starts (blockIdx.x >> 8) see the whole grid.
 struct PcBatchArgs {
-    const unsigned long long *seeds; // [B] Philox keys
-    const float *goals;              // [B][s]
     int nb;                          // tiles per member
     int u_stride;                    // floats from one member's sequence to the next (tau*a + a: the zero tail of the shift)
     int rec_stride;                  // floats from one member's record block to the next (nbp * (2 + tau*a))
@@ -243,8 +242,8 @@ __global__ __launch_bounds__(64 * (NP + 1), (NSLOT * 4 * A <= 80 ? NP + 1 : 2)) 
 #undef MPPI_PC_BATCH
 }
 
-// B controllers in one grid of B * nb tiles (PcBatchArgs): the step's one pass with the quadratic cost, diagonal or dense Q. Member m's records
-// are column-major [2 + H*a][rsc] at partials + m * rec_stride, its costs at cost + m * K.
+// B controllers in one grid of B * nb tiles (PcBatchArgs): the step's one pass with the quadratic cost, diagonal or dense Q. C is [B]: member
+// m's constants at C + m. Member m's records are column-major [2 + H*a][rsc] at partials + m * rec_stride, its costs at cost + m * K.
 template <int A, int NP, int NSLOT, bool DIAG, int COST>
 __global__ __launch_bounds__(64 * (NP + 1), (NSLOT * 4 * A <= 80 ? NP + 1 : 2)) void k_rollout_pc_batch(
     const DevConsts *__restrict__ C, const float *__restrict__ x_dev, const float *__restrict__ U_dev,
@@ -442,10 +441,11 @@ __global__ __launch_bounds__(kThreads) void k_finish_cols(
 // k_finish_cols_batch: k_finish_cols for the B members of a batched handle in ONE grid of B * HA workgroups. Workgroup w finishes column
 // c = w - m*HA of member m = w / HA from member m's records (recs + m * rec_stride, element (b, col) at [b + col*sc]) through the same
 // column_combine, so every member's U' and u carry the bits of a lone controller's finish: U'[m][c] = clip(U[m][c] + V/eta), u[m] = U'[m][0..a).
-// The Philox step counter is shared: workgroup 0 alone advances it. dbg: beta, eta of member m at dbg[8m], dbg[8m + 1].
+// The Philox step counter is shared: workgroup 0 alone advances it. dbg: beta, eta of member m at dbg[8m], dbg[8m + 1]. The temperature
+// is member m's own: C[m].neg_inv_lambda, the value a lone handle passes to k_finish_cols.
 template <int A>
 __global__ __launch_bounds__(kThreads) void k_finish_cols_batch(
-    const float *__restrict__ recs, int sc, int nb, int HA, int rec_stride, float neg_inv_lambda,
+    const float *__restrict__ recs, int sc, int nb, int HA, int rec_stride, const DevConsts *__restrict__ C,
     const float *__restrict__ U_in, float *__restrict__ U_out, int u_stride, float *__restrict__ u_out,
     unsigned long long *__restrict__ step_ctr, float *__restrict__ dbg, const float *__restrict__ clip)
 {
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(kThreads) void k_finish_cols_batch(
     float beta;
     double eta, V;
     column_combine([&](int b, int j) { return recs[(size_t)b + (size_t)(j == 2 ? 2 + c : j) * sc]; },
-                   nb, neg_inv_lambda, red_f, red_d, beta, eta, V);
+                   nb, C[m].neg_inv_lambda, red_f, red_d, beta, eta, V);
     if (tid == 0) {
         if (c == 0) { dbg[8 * m] = beta; dbg[8 * m + 1] = (float)eta; }
         const float un = fminf(fmaxf(u_old + (float)(V / eta), lo), hi);

@@ -1,5 +1,5 @@
 // mppi_launch_batch.hip — instantiates the batched step (k_rollout_pc_batch + k_finish_cols_batch, mppi_kernels.hip.h) for ONE action
-// dimension (-DMPPI_UNIT_A). B controllers that share one configuration step in the same two launches as one controller.
+// dimension (-DMPPI_UNIT_A). B controllers, each with its own constants (h->dC[m]), step in the same two launches as one controller.
 #include "mppi_handle.hip.h"
 #ifndef MPPI_UNIT_A
 #error "compile with -DMPPI_UNIT_A=<action dimension 1..4> (mppi-tf_amd/build.py)"
@@ -42,7 +42,7 @@ hipError_t MPPI_CAT(mppi_batch_a, MPPI_UNIT_A)(MPPI_PC_PARAMS)
     const size_t lds = std::max(pc_lds_floats(MPPI_UNIT_A, p.np) * 4, (size_t)h->pc_lds_min);
     const int nb = (h->K_local + 63) / 64;
     const int tiles = nb * h->batch;
-    const PcBatchArgs bt{h->d_seeds, h->d_goals, nb, h->HA + h->a, h->nbp * (2 + h->HA)};
+    const PcBatchArgs bt{nb, h->HA + h->a, h->nbp * (2 + h->HA)};
     // roles and head starts as a lone handle's, enabled by the TOTAL tile count: the whole grid must be resident in one round
     return mppi_launch(h, p.kern, dim3(tiles), dim3(64 * (p.np + 1)), lds, st, h->dC, x_dev, h->U_cur(), h->d_step, h->d_cost, h->d_part, 1,
                        h->nbp, mppi_pc_balance(h, MPPI_UNIT_A, p.nslot, tiles), (float *)nullptr, (float *)nullptr, bt);
@@ -54,7 +54,7 @@ const char *MPPI_CAT(mppi_batch_name_a, MPPI_UNIT_A)(const mppi_handle *h) { ret
 hipError_t MPPI_CAT(mppi_batch_finish_a, MPPI_UNIT_A)(MPPI_BATCH_FINISH_PARAMS)
 {
     hipExtLaunchKernelGGL(k_finish_cols_batch<MPPI_UNIT_A>, dim3(h->HA * h->batch), dim3(kThreads), 0, st, ev0, ev1, 0, (const float *)h->d_part, h->nbp,
-                          h->nbp, h->HA, h->nbp * (2 + h->HA), h->hc.neg_inv_lambda, U_in, U_out, h->HA + h->a, u_dev, h->d_step, h->d_dbg,
+                          h->nbp, h->HA, h->nbp * (2 + h->HA), (const DevConsts *)h->dC, U_in, U_out, h->HA + h->a, u_dev, h->d_step, h->d_dbg,
                           (const float *)h->d_clip);
     return hipGetLastError();
 }

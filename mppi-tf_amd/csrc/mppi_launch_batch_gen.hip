@@ -19,7 +19,7 @@ static auto pick_batch_auv(const mppi_handle *h)
 hipError_t mppi_launch_batch_auv(MPPI_PC_PARAMS)
 {
     const int wgs = (h->nb + 1) / 2 * h->batch;
-    const PcBatchArgs bt{h->d_seeds, h->d_goals, h->nb, h->HA + h->a, h->nbp * (2 + h->HA)};
+    const PcBatchArgs bt{h->nb, h->HA + h->a, h->nbp * (2 + h->HA)};
     const GenConsts *G = static_cast<const GenConsts *>(mppi_gen_dev_consts(h));
     return mppi_launch(h, pick_batch_auv(h).kern, dim3(wgs), dim3(kAuvPcThreads), 0, st, h->dC, G, x_dev, h->U_cur(), h->d_step, h->d_cost,
                        h->d_part, 1, h->nbp, h->nb, mppi_two_tile_balance(h, wgs), bt);
@@ -31,7 +31,7 @@ const char *mppi_batch_auv_name(const mppi_handle *h) { return pick_batch_auv(h)
 hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS)
 {
     hipExtLaunchKernelGGL(k_finish_cols_batch<kGenA>, dim3(h->HA * h->batch), dim3(kThreads), 0, st, ev0, ev1, 0, (const float *)h->d_part, h->nbp,
-                          h->nbp, h->HA, h->nbp * (2 + h->HA), h->hc.neg_inv_lambda, U_in, U_out, h->HA + h->a, u_dev, h->d_step, h->d_dbg,
+                          h->nbp, h->HA, h->nbp * (2 + h->HA), (const DevConsts *)h->dC, U_in, U_out, h->HA + h->a, u_dev, h->d_step, h->d_dbg,
                           (const float *)h->d_clip);
     return hipGetLastError();
 }

@@ -1,15 +1,8 @@
 // mppi_rollout_auv_pc.inc — the body of the Fossen AUVModel's two-wave rollout kernel, included as the body of k_rollout_auv_pc
 // (MPPI_AUV_BATCH 0) and of k_rollout_auv_pc_batch (MPPI_AUV_BATCH 1), both in mppi_gen.hip.h: the pattern of mppi_rollout_pc.inc. A
 // textual body, so that the lone controller's instances compile to exactly the code they had. With MPPI_AUV_BATCH 1 every per-member
-// operand moves to member m's (x, U, costs, records, the Philox key and the goal; MPPI_AUV_KEY, MPPI_AUV_GOAL below); the arithmetic of
-// every sample (noise, the two waves' Runge-Kutta stages, the cost, the tile record) is the same text.
-#if MPPI_AUV_BATCH
-#define MPPI_AUV_KEY bt.seeds[member]
-#define MPPI_AUV_GOAL (bt.goals + (size_t)member * S)
-#else
-#define MPPI_AUV_KEY C->seed
-#define MPPI_AUV_GOAL C->goal
-#endif
+// operand moves to member m's (x, U, costs, records, and C: member m's DevConsts with its Philox key, goal, lambda, gamma, upsilon, Sigma
+// and Q); the arithmetic of every sample (noise, the two waves' Runge-Kutta stages, the cost, the tile record) is the same text.
     constexpr int S = kGenS, A = kGenA;
     __shared__ float g_s[2][2][6][64];    // [tile of the workgroup][barrier parity][restoring forces g(eta) of the stage state][rollout]   A -> B
     __shared__ float vel_s[2][2][6][64];  // [tile][barrier parity][velocities of the stage state][rollout]                       B -> A
@@ -35,10 +28,11 @@
         role = __builtin_amdgcn_readfirstlane(role);
     }
 #if MPPI_AUV_BATCH
-    // member m = blockIdx.x / W of the batch (W = (n_tiles + 1) / 2 workgroups per member): its own x, U, costs, records, Philox key and
-    // goal (PcBatchArgs). tile_ok and valid below are judged against the member's own tile count and K.
+    // member m = blockIdx.x / W of the batch (W = (n_tiles + 1) / 2 workgroups per member): its own x, U, costs, records (PcBatchArgs) and
+    // constants C[m] (H and K above are shared). tile_ok and valid below are judged against the member's own tile count and K.
     const int member = (int)blockIdx.x / ((n_tiles + 1) >> 1);
     const int tile = 2 * ((int)blockIdx.x - member * ((n_tiles + 1) >> 1)) + pair;
+    C += member;
     x_dev += (size_t)member * S;
     U_dev += (size_t)member * bt.u_stride;
     cost += (size_t)member * K;
@@ -119,18 +113,13 @@
         GenQuadConsts qc;
         const bool quad_diag = C->state_cost_kind == MPPI_STATE_COST_QUADRATIC && !C->q_full;
 #pragma unroll
-        for (int i = 0; i < S; ++i) { qc.goal[i] = MPPI_AUV_GOAL[i]; qc.qdiag[i] = C->qdiag[i]; }
+        for (int i = 0; i < S; ++i) { qc.goal[i] = C->goal[i]; qc.qdiag[i] = C->qdiag[i]; }
         PcProducerConsts<A> pcst; // Sigma, Sigma^-1, lambda: a kernel-local copy (no re-fetch behind the barriers)
         pcst.template load<DIAG>(C);
         const unsigned long long base = step_ctr[0] * (unsigned long long)NG;
-        const unsigned long long seed = MPPI_AUV_KEY;
+        const unsigned long long seed = C->seed;
         const unsigned long long gk = (unsigned long long)C->k_offset + (unsigned long long)kk;
-#if MPPI_AUV_BATCH
-        const GenGoalRef gref{MPPI_AUV_GOAL, C->qfull}; // StaticQuatCost and the dense Q read the member's goal
-        auto cost_of = [&](const float (&xs)[S]) { return quad_diag ? state_cost<S, false>(&qc, xs) : gen_state_cost_goal(C, G, &gref, xs); };
-#else
         auto cost_of = [&](const float (&xs)[S]) { return quad_diag ? state_cost<S, false>(&qc, xs) : gen_state_cost(C, G, xs); };
-#endif
         float x[S], c = 0.0f, z[4 * A];
 #pragma unroll
         for (int i = 0; i < S; ++i) x[i] = x_dev[i];
@@ -236,7 +225,5 @@
     __syncthreads();
     if (MODE == MODE_COST_ONLY || !tile_ok) return;
     const float ct = cost_s[pair][lane];
-    mlp_tile_record<A, DIAG, 2>(C, ct, valid, role, lane, kk, H, NG, SRC, eps_hbm, MPPI_AUV_KEY, (unsigned long long)C->k_offset + (unsigned long long)kk,
+    mlp_tile_record<A, DIAG, 2>(C, ct, valid, role, lane, kk, H, NG, SRC, eps_hbm, C->seed, (unsigned long long)C->k_offset + (unsigned long long)kk,
                                 step_ctr[0] * (unsigned long long)NG, partials + (size_t)record_slot(tile, rsc) * rsb, rsc);
-#undef MPPI_AUV_KEY
-#undef MPPI_AUV_GOAL

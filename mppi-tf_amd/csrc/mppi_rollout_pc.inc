@@ -1,8 +1,8 @@
 // mppi_rollout_pc.inc — the body of the producer/consumer rollout kernel, included as the body of k_rollout_pc (MPPI_PC_BATCH 0) and
 // of k_rollout_pc_batch (MPPI_PC_BATCH 1), both in mppi_kernels.hip.h. A textual body rather than a force-inlined device function: the
 // single controller's instances compile to exactly the code they had (an inlined function turns the kernel's __restrict__ arguments into
-// alias scopes, and the scheduler makes other choices). With MPPI_PC_BATCH 1 every per-member operand moves to member m's; the
-// arithmetic of every sample (noise, model step, costs, tile soft-min, butterfly) is the same text.
+// alias scopes, and the scheduler makes other choices). With MPPI_PC_BATCH 1 every per-member operand moves to member m's (C points at
+// member m's DevConsts); the arithmetic of every sample (noise, model step, costs, tile soft-min, butterfly) is the same text.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int S = 2 * A;
     constexpr int NW = NP + 1;
@@ -45,9 +45,11 @@
     const int lane = tid & 63;
     unsigned blk = blockIdx.x; // the tile within its controller
 #if MPPI_PC_BATCH
-    // member m = blockIdx.x / nb of the batch: its own x, U, costs, records, Philox key and goal (PcBatchArgs)
+    // member m = blockIdx.x / nb of the batch: its own x, U, costs, records (PcBatchArgs) and constants C[m] (Philox key, goal, lambda,
+    // gamma, upsilon, Sigma, Q); H and K above are shared
     const int member = (int)blockIdx.x / bt.nb;
     blk = blockIdx.x - (unsigned)(member * bt.nb);
+    C += member;
     x_dev += (size_t)member * S;
     U_dev += (size_t)member * bt.u_stride;
     cost += (size_t)member * K;
@@ -81,11 +83,7 @@
         const int p = wave - 1;
         const unsigned int gk = (unsigned int)C->k_offset + (unsigned int)(k0 + lane); // the global sample index: below 2^31 + 64
         const unsigned long long base = step_ctr[0] * (unsigned long long)NG;
-#if MPPI_PC_BATCH
-        const unsigned long long seed = bt.seeds[member];
-#else
         const unsigned long long seed = C->seed;
-#endif
         float eps_r[NREG];
         PcProducerConsts<A> pcst; // SGPR-resident copy: no constant re-fetch after the barriers
         pcst.template load<DIAG>(C);
@@ -199,14 +197,6 @@
         PcDenseQConsts<S> qcst;
         if constexpr (COST == PC_COST_ELLIPSE) ecst.load(C);
         if constexpr (COST == PC_COST_DENSE) qcst.load(C);
-#if MPPI_PC_BATCH
-        // the member's goal, kernel-local before the first barrier like the other constants (SGPRs for the whole kernel)
-#pragma unroll
-        for (int i = 0; i < S; ++i) {
-            ccst.goal[i] = bt.goals[(size_t)member * S + i];
-            if constexpr (COST == PC_COST_DENSE) qcst.goal[i] = ccst.goal[i];
-        }
-#endif
         auto cost_of = [&](const float (&xs)[S]) {
             if constexpr (COST == PC_COST_ELLIPSE) return state_cost_ellipse<S>(&ecst, xs);
             else if constexpr (COST == PC_COST_DENSE) return state_cost_dense<S>(&qcst, xs);

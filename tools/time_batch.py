@@ -6,7 +6,12 @@ Each figure is a host clock around `steps` pipelined next_device steps (rounds o
 alternate, `reps` times, and the median is printed: us per batched step (per round for (b)), us per controller step, rollouts/s.
 --model auv: the Fossen AUV model at the reference's task (mppi_tf_amd.auv.auv_task: rexrov2, rk2, Sigma = 1500 I, the static goal),
 with the x0 of that task for every controller.
-    tools/time_batch.py [--model pm|auv] [--steps N] [--reps R] [--quick] [--only batch|streams|single] [--shape B,K,H] [--dry-run]"""
+--sweep: a parameter sweep against a uniform batch of the same shape (B = 16: the point mass at K=4096 H=64 a=2 and K=3000 H=50 a=3, the
+AUV at K=4096 H=40). In the sweep batch every member has its own lambda (log-spaced 0.1 to 10), Sigma scale (0.5 to 2) and Q scale (0.5
+to 2); the uniform batch shares the configuration. The two alternate as above. --only uniform times the uniform batch alone (through
+BatchHandle's shared keywords only, so the tool also runs on a package without per-member parameters).
+    tools/time_batch.py [--model pm|auv] [--steps N] [--reps R] [--quick] [--only batch|streams|single] [--shape B,K,H] [--dry-run]
+    tools/time_batch.py --sweep [--only sweep|uniform] [--steps N] [--reps R] [--dry-run]"""
 import argparse
 import os
 import sys
@@ -93,16 +98,70 @@ def shape(B, K, H, a, steps, reps, only=None, model="pm"):
     return med
 
 
+def sweep_kw(B, a_kw):
+    """the per-member keywords of the sweep batch: lambda log-spaced over two decades, Sigma and Q scaled by 0.5 .. 2"""
+    sc = np.linspace(0.5, 2.0, B)
+    sig, Q = np.asarray(a_kw["sigma"], np.float32), np.asarray(a_kw.get("Q", np.ones(a_kw["s_dim"])), np.float32)
+    return dict(lams=list(np.logspace(-1, 1, B)), sigmas=np.stack([f * sig for f in sc]), Qs=np.stack([f * Q for f in sc[::-1]]))
+
+
+def sweep(B, K, H, a, model, steps, reps, only=None):
+    a_kw, x0 = configs(model, K, H, a)
+    a, s = a_kw["a_dim"], a_kw["s_dim"]
+    hs = {}
+    if only != "sweep":
+        hs["uniform"] = m.BatchHandle(n=B, **a_kw)
+    if only != "uniform":
+        hs["sweep"] = m.BatchHandle(n=B, **a_kw, **sweep_kw(B, a_kw))
+    xb, ub = torch.from_numpy(np.tile(x0, (B, 1))).cuda(), torch.zeros((B, a), device="cuda")
+    assert xb.shape == (B, s)
+    runs = {k: ((lambda h=h: h.next_device(xb.data_ptr(), ub.data_ptr(), None)), h.synchronize) for k, h in hs.items()}
+    for f, sy in runs.values():
+        clock(f, sy, max(50, steps // 4))
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, (f, sy) in runs.items():
+            t[k].append(clock(f, sy, steps) / steps)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    for k in med:
+        print("B=%-2d K=%-5d H=%-3d a=%d  %-7s %8.2f us per batched step  (spread over %d reps: %.2f-%.2f us)" % (
+            B, K, H, a, k, med[k] * 1e6, reps, min(t[k]) * 1e6, max(t[k]) * 1e6), flush=True)
+    if len(med) == 2:
+        print("B=%-2d K=%-5d H=%-3d a=%d  sweep / uniform = %.3f" % (B, K, H, a, med["sweep"] / med["uniform"]), flush=True)
+    for h in hs.values():
+        h.close()
+    return med
+
+
+def main_sweep(o):
+    shapes = [("pm", 16, 4096, 64, 2), ("pm", 16, 3000, 50, 3), ("auv", 16, 4096, 40, 6)]
+    if o.dry_run:
+        for model, B, K, H, a in shapes:
+            c, _ = configs(model, K, H, a)
+            kw_ = sweep_kw(B, c)
+            print("%s B=%-2d K=%-5d H=%-3d a=%d  lambda %.3g..%.3g  %s" % (model, B, K, H, c["a_dim"], kw_["lams"][0], kw_["lams"][-1],
+                                                                       sorted(c) + sorted(kw_)), flush=True)
+        return
+    from mppi_tf_amd import _lib
+    print("tools/time_batch.py --sweep: %s, %s, steps %d, reps %d" % (torch.cuda.get_device_name(0), _lib.SO_PATH, o.steps, o.reps), flush=True)
+    for model, B, K, H, a in shapes:
+        sweep(B, K, H, a, model, o.steps, o.reps, o.only)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--quick", action="store_true", help="one shape only: B = 4, K = 4096, H = 64, a = 2")
-    ap.add_argument("--only", choices=("batch", "streams", "single"), help="time one of the three alone")
+    ap.add_argument("--only", choices=("batch", "streams", "single", "sweep", "uniform"),
+                    help="time one of the three alone (--sweep: the sweep or the uniform batch alone)")
+    ap.add_argument("--sweep", action="store_true", help="a per-member parameter sweep against the uniform batch of the same shape")
     ap.add_argument("--model", choices=("pm", "auv"), default="pm", help="pm: the point mass; auv: the Fossen AUV at the reference's task")
     ap.add_argument("--shape", help="one shape only: B,K,H (the action dimension: 2 for pm, 6 for auv)")
     ap.add_argument("--dry-run", action="store_true", help="print the shapes and build their configurations, time nothing (no GPU)")
     o = ap.parse_args()
+    if o.sweep:
+        return main_sweep(o)
     if o.model == "auv":
         shapes = ([(B, 4096, 40, 6) for B in (1, 2, 4, 8, 16)] + [(B, 16384, 40, 6) for B in (1, 2, 4, 8, 16)]
                   + [(B, 65536, 64, 6) for B in (1, 2)])

@@ -304,8 +304,8 @@ static mppi_status upload_mlp(mppi_handle *h, const mppi_mlp_desc *d, bool alloc
     return MPPI_OK;
 }
 
-// The constants of one controller from its config, on the geometry mppi_create derived (K_local, k_offset, H, s, a): mppi_create's, and
-// once per member in mppi_create_batch_configs. sigma_diag: 1 when Σ and Σ⁻¹ are diagonal (the DIAG instances). false: Σ is singular.
+// The constants of one controller from its config, on the geometry derive_handle set (K_local, k_offset, H, s, a): once per member
+// (member_consts). sigma_diag: 1 when Σ and Σ⁻¹ are diagonal (the DIAG instances). false: Σ is singular.
 static bool fill_consts(const mppi_config *cfg, const mppi_handle *h, DevConsts &c, int &sigma_diag)
 {
     const int s = h->s, a = h->a;
@@ -352,15 +352,19 @@ static bool fill_consts(const mppi_config *cfg, const mppi_handle *h, DevConsts 
     return true;
 }
 
-extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
+// ---- creation: validate the config, derive the handle's geometry, fill every member's constants, allocate ---------------------------------
+// On the host a lone handle is the one-member case of a batch's layout (mppi_handle.hip.h, `batch`): mppi_create and the batch creators
+// run the same three steps and the same allocation, at members(h) = 1 and n.
+static const char *const kBadTemperature = "lambda must be > 0, upsilon != 0";
+static bool temperature_ok(const mppi_config *cfg) { return cfg->lambda > 0.0f && cfg->upsilon != 0.0f; }
+
+// what a config alone tells (no handle yet), then that a device serves it
+static mppi_status validate_config(const mppi_config *cfg)
 {
-    if (!cfg || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfg/out is NULL");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(mppi_config)) return fail(nullptr, MPPI_ERR_INVALID_ARG, "mppi_config.struct_size mismatch (use mppi_config_init)");
     const int s = cfg->s_dim, a = cfg->a_dim;
     if (cfg->k <= 0 || cfg->tau <= 0 || s <= 0 || a <= 0 || s > kMaxS || a > kMaxA)
         return fail(nullptr, MPPI_ERR_INVALID_ARG, "k, tau, s_dim, a_dim out of range");
-    if (!(cfg->lambda > 0.0f) || !(cfg->upsilon != 0.0f)) return fail(nullptr, MPPI_ERR_INVALID_ARG, "lambda must be > 0, upsilon != 0");
+    if (!temperature_ok(cfg)) return fail(nullptr, MPPI_ERR_INVALID_ARG, kBadTemperature);
     if (cfg->shard_count < 1 || cfg->shard_rank < 0 || cfg->shard_rank >= cfg->shard_count)
         return fail(nullptr, MPPI_ERR_INVALID_ARG, "bad shard_rank/shard_count");
     if (cfg->model_kind == MPPI_MODEL_POINT_MASS && !(cfg->mass != 0.0f)) return fail(nullptr, MPPI_ERR_INVALID_ARG, "mass must be non-zero");
@@ -416,7 +420,14 @@ extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
     int ndev = mppi_device_count();
     if (ndev <= 0) return fail(nullptr, MPPI_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, MPPI_ERR_NO_DEVICE, "device ordinal out of range");
+    return MPPI_OK;
+}
 
+// the handle of cfg's geometry, kernel flags and record count: nothing on the device yet, no constants
+static mppi_status derive_handle(const mppi_config *cfg, mppi_handle **out)
+{
+    const int s = cfg->s_dim, a = cfg->a_dim;
+    const bool gen = cfg->model_kind == MPPI_MODEL_AUV || cfg->model_kind == MPPI_MODEL_NN_AUV || cfg->model_kind == MPPI_MODEL_NN_AUV_SPEED;
     mppi_handle *h = new (std::nothrow) mppi_handle();
     if (!h) return fail(nullptr, MPPI_ERR_ALLOC, "out of host memory");
     h->device = cfg->device;
@@ -431,8 +442,6 @@ extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
     // 5 producers shorten a lone tile's pipeline (15.6 vs 18.3 us at 1 tile/CU) but cost throughput once
     // >= 4 tiles share a CU (the kernel is VALU-issue bound there): pick by tiles per CU.
     h->pc_np = ((h->K_local + 63) / 64 <= 2 * 256) ? 5 : 3;
-
-    if (!fill_consts(cfg, h, h->hc, h->sigma_diag)) { delete h; return fail(nullptr, MPPI_ERR_SINGULAR_SIGMA, "sigma is singular"); }
 
     // tile geometry: the largest R in {64,32,16} whose LDS image fits one CU (160 KiB), preferring
     // <= ~53 KiB so three workgroups share a CU.
@@ -455,73 +464,126 @@ extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
     h->is_gen = gen ? 1 : 0;
     h->mlp_v2 = (cfg->model_kind == MPPI_MODEL_MLP && !h->mlp_small && !h->mlp_bx3 && a <= 3) ? 1 : 0; // a_dim = 4: two h1 images + the rest exceed 160 KiB of LDS
     h->nb_mlp = cfg->model_kind == MPPI_MODEL_MLP ? (h->mlp_v2 ? (h->K_local + kMlp2R - 1) / kMlp2R : (h->K_local + kMlpR - 1) / kMlpR) : 0;
+    h->nbp = record_pad(std::max(h->nb, h->nb_mlp));
+    *out = h;
+    return MPPI_OK;
+}
 
-    mppi_status st = MPPI_OK;
-    auto body = [&]() -> mppi_status {
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        HIP_TRY(h, hipMalloc((void **)&h->dC, sizeof(DevConsts)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_x, sizeof(float) * kMaxS));
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(h, hipMalloc((void **)&h->d_Ubuf[i], sizeof(float) * (h->HA + h->a)));
-            HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, sizeof(float) * (h->HA + h->a), h->stream)); // U0 = 0
+// Member m's constants from its config, the one validation of a member: its temperature, its Sigma, and that it runs the kernel instance
+// member 0 picked (sigma_diag, the effective Q form; member 0 is filled into h->hc and sets both). A failure is g_create_err, naming the member if `named`.
+static mppi_status member_consts(const mppi_config *cfg, int m, bool named, mppi_handle *h, DevConsts &c)
+{
+    const std::string who = named ? "batched controllers: member " + std::to_string(m) + ": " : "";
+    if (!temperature_ok(cfg)) return fail(nullptr, MPPI_ERR_INVALID_ARG, who + kBadTemperature);
+    int diag = 0;
+    if (!fill_consts(cfg, h, c, diag)) return fail(nullptr, MPPI_ERR_SINGULAR_SIGMA, who + "sigma is singular");
+    if (m == 0) { h->sigma_diag = diag; return MPPI_OK; } // (c is h->hc: member 0 sets what the others are compared with)
+    if (diag != h->sigma_diag)
+        return fail(nullptr, MPPI_ERR_UNSUPPORTED, "batched controllers: sigma must be diagonal for every member or dense for every member (member " + std::to_string(m) + " differs from member 0)");
+    if (c.q_full != h->hc.q_full)
+        return fail(nullptr, MPPI_ERR_UNSUPPORTED, "batched controllers: Q must be diagonal for every member or dense for every member (member " + std::to_string(m) +
+                                                       " differs from member 0; a dense Q without off-diagonal entries counts as diagonal)");
+    return MPPI_OK;
+}
+
+// Everything mppi_create reports for cfg before it allocates: the config, the geometry, member 0's constants (h->hc), the 13-state constants.
+// member0: the error names member 0 (mppi_create_batch_configs).
+static mppi_status prepare_handle(const mppi_config *cfg, bool member0, mppi_handle **out)
+{
+    auto named = [&](mppi_status st) { return member0 ? fail(nullptr, st, "batched controllers: member 0: " + g_create_err) : st; };
+    if (mppi_status st = validate_config(cfg); st != MPPI_OK) return named(st);
+    mppi_handle *h = nullptr;
+    if (mppi_status st = derive_handle(cfg, &h); st != MPPI_OK) return named(st);
+    mppi_status st = member_consts(cfg, 0, member0, h, h->hc);
+    if (st == MPPI_OK && (h->is_gen || cfg->state_cost_kind == MPPI_STATE_COST_QUAT || cfg->state_cost_kind == MPPI_STATE_COST_ELLIPSE3D))
+        if (const char *why = mppi_gen_fill(h, cfg)) st = named(fail(nullptr, MPPI_ERR_INVALID_ARG, why));
+    if (st != MPPI_OK) { mppi_destroy(h); return st; }
+    *out = h;
+    return MPPI_OK;
+}
+
+// The device side of a prepared handle with B = members(h) members, whose constants are consts[0..B): the per-member buffers (U, costs,
+// records, dbg words, constants) at B times their stride, the rest once. On a failure the caller destroys h (h->err says why).
+static mppi_status allocate_handle(mppi_handle *h, const mppi_config *cfg, int B, const DevConsts *consts)
+{
+    const size_t K = (size_t)h->K_local, rec = (size_t)h->nbp * (2 + h->HA), us = (size_t)h->HA + h->a;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
+    HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIP_TRY(h, hipMalloc((void **)&h->dC, sizeof(DevConsts) * B));
+    HIP_TRY(h, hipMalloc((void **)&h->d_x, sizeof(float) * kMaxS));
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(h, hipMalloc((void **)&h->d_Ubuf[i], sizeof(float) * us * B));
+        HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, sizeof(float) * us * B, h->stream)); // U0 = 0, zero tails
+    }
+    HIP_TRY(h, hipMalloc((void **)&h->d_u, sizeof(float) * kMaxA));
+    HIP_TRY(h, hipMalloc((void **)&h->d_cost, sizeof(float) * K * B));
+    HIP_TRY(h, hipMalloc((void **)&h->d_cost2, sizeof(float) * h->K_local));
+    // every member's record block with its neutral pads
+    const int nrec = h->nbp;
+    HIP_TRY(h, hipMalloc((void **)&h->d_part, sizeof(float) * rec * B));
+    for (int m = 0; m < B; ++m)
+        hipLaunchKernelGGL(k_fill_records, dim3((unsigned)((rec + 255) / 256)), dim3(256), 0, h->stream, h->d_part + rec * m, nrec, 2 + h->HA);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // steps may be enqueued on the caller's stream
+    const int nrec2 = (nrec + kGroup - 1) / kGroup, nrec3 = (nrec2 + kGroup - 1) / kGroup;
+    HIP_TRY(h, hipMalloc((void **)&h->d_part2, sizeof(float) * (size_t)nrec2 * (2 + h->HA)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_part3, sizeof(float) * (size_t)nrec3 * (2 + h->HA)));
+    if (cfg->model_kind == MPPI_MODEL_MLP || cfg->model_kind == MPPI_MODEL_NN_AUV || cfg->model_kind == MPPI_MODEL_NN_AUV_SPEED) {
+        if (mppi_status st_ = upload_mlp(h, cfg->mlp, true); st_ != MPPI_OK) return st_;
+    }
+    HIP_TRY(h, hipMalloc((void **)&h->d_record, sizeof(float) * (2 + h->HA)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_dbg, sizeof(float) * 8 * B));
+    HIP_TRY(h, hipMalloc((void **)&h->d_mm, sizeof(float) * 4));
+    if (h->normalize) HIP_TRY(h, hipMalloc((void **)&h->d_tile_mm, sizeof(float) * 2 * (size_t)nrec));
+    HIP_TRY(h, hipMalloc((void **)&h->d_step, sizeof(unsigned long long)));
+    if (h->shard_count > 1) { // mppi_shard_step's buffers: allocated here, not inside the enqueue-only step (an allocation there is an implicit device sync)
+        HIP_TRY(h, hipMalloc((void **)&h->d_recs, sizeof(float) * (size_t)(2 + h->HA) * h->shard_count));
+        HIP_TRY(h, hipMalloc((void **)&h->d_range, sizeof(float) * 2));
+    }
+    HIP_TRY(h, hipHostMalloc((void **)&h->h_pin, sizeof(float) * (2 * kMaxS + kMaxA), hipHostMallocMapped));
+    HIP_TRY(h, hipHostGetDevicePointer((void **)&h->d_pin, h->h_pin, 0));
+    HIP_TRY(h, hipMemsetAsync(h->d_step, 0, sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, sizeof(float) * 8 * B, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_cost, 0, sizeof(float) * K * B, h->stream));
+    if (!h->batch && !h->is_gen && cfg->model_kind == MPPI_MODEL_POINT_MASS && h->no_rollout.empty() && h->R == 64) {
+        // the whole step in one launch / the armed launch (mppi_step.hip.h): record granules of a <= 128-tile grid, the verdict words,
+        // and the x slot the HOST stores into — fine-grained device memory, reachable from the CPU only on a large-BAR system
+        // (without one d_xslot stays NULL and MPPI_TUNE_ARMED_US answers MPPI_ERR_UNSUPPORTED)
+        if (h->nb <= 128) {
+            HIP_TRY(h, hipMalloc((void **)&h->d_step_recs, sizeof(unsigned long long) * (size_t)(2 + h->HA) * 128));
+            HIP_TRY(h, hipMemsetAsync(h->d_step_recs, 0, sizeof(unsigned long long) * (size_t)(2 + h->HA) * 128, h->stream));
         }
-        HIP_TRY(h, hipMalloc((void **)&h->d_u, sizeof(float) * kMaxA));
-        HIP_TRY(h, hipMalloc((void **)&h->d_cost, sizeof(float) * h->K_local));
-        HIP_TRY(h, hipMalloc((void **)&h->d_cost2, sizeof(float) * h->K_local));
-        const int nrec = h->nbp = record_pad(std::max(h->nb, h->nb_mlp));
-        HIP_TRY(h, hipMalloc((void **)&h->d_part, sizeof(float) * (size_t)nrec * (2 + h->HA)));
-        hipLaunchKernelGGL(k_fill_records, dim3((nrec * (2 + h->HA) + 255) / 256), dim3(256), 0, h->stream, h->d_part, nrec, 2 + h->HA);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipStreamSynchronize(h->stream)); // steps may be enqueued on the caller's stream
-        const int nrec2 = (nrec + kGroup - 1) / kGroup, nrec3 = (nrec2 + kGroup - 1) / kGroup;
-        HIP_TRY(h, hipMalloc((void **)&h->d_part2, sizeof(float) * (size_t)nrec2 * (2 + h->HA)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_part3, sizeof(float) * (size_t)nrec3 * (2 + h->HA)));
-        if (cfg->model_kind == MPPI_MODEL_MLP || cfg->model_kind == MPPI_MODEL_NN_AUV || cfg->model_kind == MPPI_MODEL_NN_AUV_SPEED) {
-            if (mppi_status st_ = upload_mlp(h, cfg->mlp, true); st_ != MPPI_OK) return st_;
-        }
-        HIP_TRY(h, hipMalloc((void **)&h->d_record, sizeof(float) * (2 + h->HA)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_dbg, sizeof(float) * 8));
-        HIP_TRY(h, hipMalloc((void **)&h->d_mm, sizeof(float) * 4));
-        if (h->normalize) HIP_TRY(h, hipMalloc((void **)&h->d_tile_mm, sizeof(float) * 2 * (size_t)nrec));
-        HIP_TRY(h, hipMalloc((void **)&h->d_step, sizeof(unsigned long long)));
-        if (h->shard_count > 1) { // mppi_shard_step's buffers: allocated here, not inside the enqueue-only step (an allocation there is an implicit device sync)
-            HIP_TRY(h, hipMalloc((void **)&h->d_recs, sizeof(float) * (size_t)(2 + h->HA) * h->shard_count));
-            HIP_TRY(h, hipMalloc((void **)&h->d_range, sizeof(float) * 2));
-        }
-        HIP_TRY(h, hipHostMalloc((void **)&h->h_pin, sizeof(float) * (2 * kMaxS + kMaxA), hipHostMallocMapped));
-        HIP_TRY(h, hipHostGetDevicePointer((void **)&h->d_pin, h->h_pin, 0));
-        HIP_TRY(h, hipMemsetAsync(h->d_step, 0, sizeof(unsigned long long), h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, sizeof(float) * 8, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_cost, 0, sizeof(float) * h->K_local, h->stream));
-        if (!gen && cfg->model_kind == MPPI_MODEL_POINT_MASS && h->no_rollout.empty() && h->R == 64) {
-            // the whole step in one launch / the armed launch (mppi_step.hip.h): record granules of a <= 128-tile grid, the verdict words,
-            // and the x slot the HOST stores into — fine-grained device memory, reachable from the CPU only on a large-BAR system
-            // (without one d_xslot stays NULL and MPPI_TUNE_ARMED_US answers MPPI_ERR_UNSUPPORTED)
-            if (h->nb <= 128) {
-                HIP_TRY(h, hipMalloc((void **)&h->d_step_recs, sizeof(unsigned long long) * (size_t)(2 + h->HA) * 128));
-                HIP_TRY(h, hipMemsetAsync(h->d_step_recs, 0, sizeof(unsigned long long) * (size_t)(2 + h->HA) * 128, h->stream));
-            }
-            HIP_TRY(h, hipMalloc((void **)&h->d_decision, 64));
-            HIP_TRY(h, hipMemsetAsync(h->d_decision, 0, 64, h->stream));
-            HIP_TRY(h, hipHostMalloc((void **)&h->h_arm, 64, hipHostMallocMapped));
-            HIP_TRY(h, hipHostGetDevicePointer((void **)&h->d_arm, h->h_arm, 0));
-            std::memset(h->h_arm, 0, 64);
-            int large_bar = 0;
-            if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) != hipSuccess) { large_bar = 0; (void)hipGetLastError(); }
-            if (large_bar && hipExtMallocWithFlags((void **)&h->d_xslot, 256, hipDeviceMallocFinegrained) == hipSuccess)
-                HIP_TRY(h, hipMemsetAsync(h->d_xslot, 0, 256, h->stream));
-            else { h->d_xslot = nullptr; (void)hipGetLastError(); }
-        }
-        if (gen || cost13) {
-            if (const char *why = mppi_gen_fill(h, cfg)) return fail(h, MPPI_ERR_INVALID_ARG, why);
-            HIP_TRY(h, mppi_gen_upload(h));
-        }
-        return upload_consts(h);
-    };
-    st = body();
-    if (st != MPPI_OK) { g_create_err = h->err; mppi_destroy(h); return st; }
+        HIP_TRY(h, hipMalloc((void **)&h->d_decision, 64));
+        HIP_TRY(h, hipMemsetAsync(h->d_decision, 0, 64, h->stream));
+        HIP_TRY(h, hipHostMalloc((void **)&h->h_arm, 64, hipHostMallocMapped));
+        HIP_TRY(h, hipHostGetDevicePointer((void **)&h->d_arm, h->h_arm, 0));
+        std::memset(h->h_arm, 0, 64);
+        int large_bar = 0;
+        if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) != hipSuccess) { large_bar = 0; (void)hipGetLastError(); }
+        if (large_bar && hipExtMallocWithFlags((void **)&h->d_xslot, 256, hipDeviceMallocFinegrained) == hipSuccess)
+            HIP_TRY(h, hipMemsetAsync(h->d_xslot, 0, 256, h->stream));
+        else { h->d_xslot = nullptr; (void)hipGetLastError(); }
+    }
+    if (h->gen) HIP_TRY(h, mppi_gen_upload(h));
+    if (h->batch) { // a batch's x and u staging; its records are laid out once, for the batched rollout's nb tiles per member
+        HIP_TRY(h, hipMalloc((void **)&h->d_bx, sizeof(float) * (size_t)B * h->s));
+        HIP_TRY(h, hipMalloc((void **)&h->d_bu, sizeof(float) * (size_t)B * h->a));
+        h->part_nb = h->nb;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->dC, consts, sizeof(DevConsts) * B, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
+{
+    if (!cfg || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfg/out is NULL");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(mppi_config)) return fail(nullptr, MPPI_ERR_INVALID_ARG, "mppi_config.struct_size mismatch (use mppi_config_init)");
+    mppi_handle *h = nullptr;
+    if (mppi_status st = prepare_handle(cfg, false, &h); st != MPPI_OK) return st;
+    if (mppi_status st = allocate_handle(h, cfg, 1, &h->hc); st != MPPI_OK) { g_create_err = h->err; mppi_destroy(h); return st; }
     *out = h;
     return MPPI_OK;
 }
@@ -886,15 +948,29 @@ extern "C" mppi_status mppi_profile_end(mppi_handle *h, float *rollout_ms_avg, f
     return MPPI_OK;
 }
 
+// ---- state that a lone handle and a batch keep alike: each accessor serves members(h) members at the strides of mppi_handle.hip.h, and the
+// public entry points (mppi_* for a lone handle, mppi_batch_* for a batch) are their argument checks plus a call.
+// goals [members(h)][s] into the members' constants, the one copy the kernels read; hc mirrors member 0's. A lone handle uploads its whole
+// block, so what the host changed in hc goes with the goal.
+static mppi_status set_goals(mppi_handle *h, const float *goals)
+{
+    MPPI_ENTER(h);
+    if (h->batch) {
+        const size_t row = sizeof(float) * h->s;
+        HIP_TRY(h, hipMemcpy2DAsync((char *)h->dC + offsetof(DevConsts, goal), sizeof(DevConsts), goals, row, row, h->batch, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    for (int i = 0; i < h->s; ++i) h->hc.goal[i] = goals[i];
+    return h->batch ? MPPI_OK : upload_consts(h);
+}
+
 extern "C" mppi_status mppi_set_goal(mppi_handle *h, const float *goal, int n)
 {
     MPPI_NOT_BATCH(h, "mppi_set_goal");
     if (!h) return MPPI_ERR_INVALID_ARG;
     if (!goal || n != h->s) // "Wrong goal size, it should match the state dimension" controller_base.cpp:127-130
         return fail(h, MPPI_ERR_INVALID_ARG, "wrong goal size, it should match the state dimension");
-    MPPI_ENTER(h);
-    for (int i = 0; i < n; ++i) h->hc.goal[i] = goal[i];
-    return upload_consts(h);
+    return set_goals(h, goal);
 }
 
 extern "C" mppi_status mppi_set_mlp(mppi_handle *h, const mppi_mlp_desc *d)
@@ -1581,15 +1657,33 @@ extern "C" mppi_status mppi_set_tuning(mppi_handle *h, int what, int value)
 }
 
 // ----------------------------------------------------------------------------------------
+// every member's sequence [members(h)][tau * a] out of / into its U block (HA + a floats: the sequence and its zero tail)
+static mppi_status get_sequences(mppi_handle *h, float *U)
+{
+    MPPI_ENTER(h);
+    const size_t row = sizeof(float) * h->HA, pitch = sizeof(float) * (h->HA + h->a);
+    HIP_TRY(h, hipMemcpy2DAsync(U, row, h->U_cur(), pitch, row, members(h), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MPPI_OK;
+}
+
+static mppi_status set_sequences(mppi_handle *h, const float *U)
+{
+    MPPI_ENTER(h);
+    const size_t row = sizeof(float) * h->HA, pitch = sizeof(float) * (h->HA + h->a);
+    for (int i = 0; i < 2; ++i) HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, pitch * members(h), h->stream)); // zero tails
+    h->u_cur = 0; h->u_off = 0; h->d_Uupd = nullptr;
+    HIP_TRY(h, hipMemcpy2DAsync(h->d_Ubuf[0], pitch, U, row, row, members(h), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MPPI_OK;
+}
+
 extern "C" mppi_status mppi_get_action_sequence(mppi_handle *h, float *U, int n)
 {
     MPPI_NOT_BATCH(h, "mppi_get_action_sequence");
     if (!h) return MPPI_ERR_INVALID_ARG;
     if (!U || n != h->HA) return fail(h, MPPI_ERR_INVALID_ARG, "U must hold tau*a floats");
-    MPPI_ENTER(h);
-    HIP_TRY(h, hipMemcpyAsync(U, h->U_cur(), sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return MPPI_OK;
+    return get_sequences(h, U);
 }
 
 extern "C" mppi_status mppi_set_action_sequence(mppi_handle *h, const float *U, int n)
@@ -1597,12 +1691,7 @@ extern "C" mppi_status mppi_set_action_sequence(mppi_handle *h, const float *U, 
     MPPI_NOT_BATCH(h, "mppi_set_action_sequence");
     if (!h) return MPPI_ERR_INVALID_ARG;
     if (!U || n != h->HA) return fail(h, MPPI_ERR_INVALID_ARG, "U must hold tau*a floats");
-    MPPI_ENTER(h);
-    for (int i = 0; i < 2; ++i) HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, sizeof(float) * (h->HA + h->a), h->stream)); // zero tails
-    h->u_cur = 0; h->u_off = 0; h->d_Uupd = nullptr;
-    HIP_TRY(h, hipMemcpyAsync(h->d_Ubuf[0], U, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return MPPI_OK;
+    return set_sequences(h, U);
 }
 
 extern "C" mppi_status mppi_get_step_counter(mppi_handle *h, uint64_t *step)
@@ -1626,50 +1715,63 @@ extern "C" mppi_status mppi_set_step_counter(mppi_handle *h, uint64_t step)
     return MPPI_OK;
 }
 
-extern "C" mppi_status mppi_debug_get(mppi_handle *h, int what, float *out, size_t n)
+// h->dC is member m's constants for the guard's scope: the lone kernels' launchers read the handle's constants there
+struct MemberConsts {
+    mppi_handle *h;
+    DevConsts *own;
+    MemberConsts(mppi_handle *h_, int m) : h(h_), own(h_->dC) { h->dC = own + m; }
+    ~MemberConsts() { h->dC = own; }
+};
+
+// one debug item of member `member` (a lone handle: 0)
+static mppi_status debug_get(mppi_handle *h, int member, int what, float *out, size_t n)
 {
-    MPPI_NOT_BATCH(h, "mppi_debug_get");
-    if (!h || !out) return h ? fail(h, MPPI_ERR_INVALID_ARG, "out is NULL") : MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h);
     const size_t K = (size_t)h->K_local;
     const float *src = nullptr;
     size_t need = 0;
     float *tmp = nullptr;
+    const float *cost = h->d_cost + K * member, *dbg = h->d_dbg + 8 * (size_t)member;
     switch (what) {
-    case MPPI_DBG_COSTS: src = h->d_cost; need = K; break;
-    case MPPI_DBG_BETA: src = h->d_dbg; need = 1; break;
-    case MPPI_DBG_ETA: src = h->d_dbg + 1; need = 1; break;
-    case MPPI_DBG_AUX: src = h->d_dbg; need = 8; break; // beta, eta, and what a timing-study build left in the other words
+    case MPPI_DBG_COSTS: src = cost; need = K; break;
+    case MPPI_DBG_BETA: src = dbg; need = 1; break;
+    case MPPI_DBG_ETA: src = dbg + 1; need = 1; break;
+    case MPPI_DBG_AUX: src = dbg; need = 8; break; // beta, eta, and what a timing-study build left in the other words
     case MPPI_DBG_U_UPDATED: // U' of the last step = the current buffer from offset 0 (the warm start reads it from offset a)
-        if (!h->d_Uupd) return fail(h, MPPI_ERR_INVALID_ARG, "no step has run since the action sequence was set");
-        src = h->d_Uupd; need = (size_t)h->HA; break;
+        if (!h->d_Uupd) return fail(h, MPPI_ERR_INVALID_ARG, h->batch ? "no step has run since the action sequences were set" : "no step has run since the action sequence was set");
+        src = h->d_Uupd + (size_t)(h->HA + h->a) * member; need = (size_t)h->HA; break;
     case MPPI_DBG_WEIGHTS: {
         need = K;
         if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
         HIP_TRY(h, hipMalloc((void **)&tmp, sizeof(float) * K));
-        // (two-pass normalizeCost: the raw costs at the step's temperature = the normalised costs at lambda)
-        hipLaunchKernelGGL(k_weights, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, (const DevConsts *)h->dC,
-                           (h->normalize && !h->norm_two_pass) ? h->d_cost2 : h->d_cost, (int)K, h->d_dbg, (float *)nullptr, (float *)nullptr, tmp,
+        // (a lone handle's two-pass normalizeCost: the raw costs at the step's temperature = the normalised costs at lambda)
+        hipLaunchKernelGGL(k_weights, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, (const DevConsts *)(h->dC + member),
+                           (h->normalize && !h->norm_two_pass) ? (const float *)h->d_cost2 : cost, (int)K, dbg, (float *)nullptr, (float *)nullptr, tmp,
                            h->norm_two_pass ? (const float *)(h->d_mm + 2) : (const float *)nullptr);
         src = tmp;
         break;
     }
     case MPPI_DBG_NOISE: {
-        // regenerate the noise of the LAST step from its Philox counters (step-1)
+        // the member's noise of the LAST step, regenerated from its Philox key and Sigma at the previous step counter (step-1)
         need = K * (size_t)h->HA;
         if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
-        mppi_status s = ensure_eps(h);
-        if (s != MPPI_OK) return s;
+        if (mppi_status s = ensure_eps(h); s != MPPI_OK) return s;
         unsigned long long cur = 0;
         HIP_TRY(h, hipMemcpyAsync(&cur, h->d_step, sizeof(cur), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (cur == 0) return fail(h, MPPI_ERR_INVALID_ARG, "no step has run yet");
-        unsigned long long prev = cur - 1;
+        const unsigned long long prev = cur - 1;
         HIP_TRY(h, hipMemcpyAsync(h->d_step, &prev, sizeof(prev), hipMemcpyHostToDevice, h->stream));
-        // noise-only pass of the tile kernel: reads neither x nor any cost buffer and writes nothing but d_eps
-        if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps));
-        else HIP_TRY(h, launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps));
+        // noise-only pass of the tile kernel (the point mass) or of k_rollout_gen (the 13-state family), on the member's constants: reads
+        // neither x nor any cost buffer and writes nothing but d_eps
+        hipError_t le;
+        {
+            MemberConsts own(h, member);
+            le = h->is_gen ? mppi_launch_gen(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps)
+                           : launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
+        }
         HIP_TRY(h, hipMemcpyAsync(h->d_step, &cur, sizeof(cur), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, le);
         src = h->d_eps;
         break;
     }
@@ -1681,6 +1783,13 @@ extern "C" mppi_status mppi_debug_get(mppi_handle *h, int what, float *out, size
     if (tmp) (void)hipFree(tmp);
     HIP_TRY(h, e);
     return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_debug_get(mppi_handle *h, int what, float *out, size_t n)
+{
+    MPPI_NOT_BATCH(h, "mppi_debug_get");
+    if (!h || !out) return h ? fail(h, MPPI_ERR_INVALID_ARG, "out is NULL") : MPPI_ERR_INVALID_ARG;
+    return debug_get(h, 0, what, out, n);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -1990,9 +2099,9 @@ static const char *batch_shared_diff(const mppi_config *a, const mppi_config *b)
     return nullptr;
 }
 
-// The batch of n members cfgs[0..n) (n >= 1). The handle is mppi_create(&cfgs[0])'s with B-fold per-member buffers, and B DevConsts blocks,
-// member m's filled from cfgs[m] exactly as mppi_create fills a lone handle's. name_members: prefix what mppi_create reports for cfgs[0]
-// with the member (mppi_create_batch_configs); mppi_create_batch keeps the messages it always gave.
+// The batch of n members cfgs[0..n) (n >= 1): the handle mppi_create(&cfgs[0]) prepares, allocated for n members, member m's DevConsts
+// block filled from cfgs[m] exactly as a lone handle's. name_members: what mppi_create reports for cfgs[0] names member 0
+// (mppi_create_batch_configs); mppi_create_batch keeps the messages it always gave.
 static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_members, mppi_handle **out)
 {
     for (int m = 0; m < n; ++m)
@@ -2003,62 +2112,20 @@ static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_member
     const mppi_config *cfg = &cfgs[0];
     if (const char *why = batch_refusal(cfg)) return fail(nullptr, MPPI_ERR_UNSUPPORTED, why);
     mppi_handle *h = nullptr;
-    if (mppi_status st = mppi_create(cfg, &h); st != MPPI_OK) {
-        if (name_members) return fail(nullptr, st, "batched controllers: member 0: " + g_create_err);
-        return st;
-    }
+    if (mppi_status st = prepare_handle(cfg, name_members, &h); st != MPPI_OK) return st;
     auto refuse = [&](mppi_status st, const std::string &why) { mppi_destroy(h); return fail(nullptr, st, why); };
     if (!h->is_gen && !pc_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: the producer/consumer rollout serves this shape only with s_dim = 2 a_dim, a_dim <= 4, tau <= 160 (<= 132 above 512 tiles)");
     if (h->is_gen && !auv_batch_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: the Fossen AUV model is batched on its two-wave rollout (k_rollout_auv_pc) only");
     if (h->nbp > 1024) return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: at most 1024 tiles (k = 65536) per member (the finish combines a member's records in one pass)");
     if ((long long)h->nb * n > (1ll << 30) / 64) return refuse(MPPI_ERR_INVALID_ARG, "batched controllers: n * k too large");
-    const int B = n, s = h->s, a = h->a, HA = h->HA;
-    // every member's constants; all members must run the instance member 0's lone handle picks (sigma_diag, the effective Q form)
-    std::vector<DevConsts> consts(B);
+    // every member's constants; all members must run the instance member 0's lone handle picks
+    std::vector<DevConsts> consts(n);
     consts[0] = h->hc;
-    for (int m = 1; m < B; ++m) {
-        if (!(cfgs[m].lambda > 0.0f) || !(cfgs[m].upsilon != 0.0f))
-            return refuse(MPPI_ERR_INVALID_ARG, "batched controllers: member " + std::to_string(m) + ": lambda must be > 0, upsilon != 0");
-        int diag = 0;
-        if (!fill_consts(&cfgs[m], h, consts[m], diag)) return refuse(MPPI_ERR_SINGULAR_SIGMA, "batched controllers: member " + std::to_string(m) + ": sigma is singular");
-        if (diag != h->sigma_diag)
-            return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: sigma must be diagonal for every member or dense for every member (member " + std::to_string(m) + " differs from member 0)");
-        if (consts[m].q_full != h->hc.q_full)
-            return refuse(MPPI_ERR_UNSUPPORTED, "batched controllers: Q must be diagonal for every member or dense for every member (member " + std::to_string(m) +
-                                                    " differs from member 0; a dense Q without off-diagonal entries counts as diagonal)");
-    }
-    const size_t K = (size_t)h->K_local, rec = (size_t)h->nbp * (2 + HA), us = (size_t)HA + a;
-    auto body = [&]() -> mppi_status {
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        // the per-member buffers replace the single controller's (same names, B times the size)
-        for (float **p : {&h->d_Ubuf[0], &h->d_Ubuf[1], &h->d_cost, &h->d_part, &h->d_dbg}) { HIP_TRY(h, hipFree(*p)); *p = nullptr; }
-        HIP_TRY(h, hipFree(h->dC));
-        h->dC = nullptr;
-        HIP_TRY(h, hipMalloc((void **)&h->dC, sizeof(DevConsts) * B));
-        HIP_TRY(h, hipMemcpyAsync(h->dC, consts.data(), sizeof(DevConsts) * B, hipMemcpyHostToDevice, h->stream));
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(h, hipMalloc((void **)&h->d_Ubuf[i], sizeof(float) * us * B));
-            HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, sizeof(float) * us * B, h->stream)); // U0 = 0, zero tails
-        }
-        HIP_TRY(h, hipMalloc((void **)&h->d_cost, sizeof(float) * K * B));
-        HIP_TRY(h, hipMemsetAsync(h->d_cost, 0, sizeof(float) * K * B, h->stream));
-        HIP_TRY(h, hipMalloc((void **)&h->d_dbg, sizeof(float) * 8 * B));
-        HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, sizeof(float) * 8 * B, h->stream));
-        // every member's record block with its neutral pads, written once (ensure_record_layout of a lone handle)
-        HIP_TRY(h, hipMalloc((void **)&h->d_part, sizeof(float) * rec * B));
-        for (int m = 0; m < B; ++m)
-            hipLaunchKernelGGL(k_fill_records, dim3((unsigned)((rec + 255) / 256)), dim3(256), 0, h->stream, h->d_part + rec * m, h->nbp, 2 + HA);
-        HIP_TRY(h, hipGetLastError());
-        h->part_nb = h->nb;
-        HIP_TRY(h, hipMalloc((void **)&h->d_bx, sizeof(float) * (size_t)B * s));
-        HIP_TRY(h, hipMalloc((void **)&h->d_bu, sizeof(float) * (size_t)B * a));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return MPPI_OK;
-    };
-    h->batch = B;
+    for (int m = 1; m < n; ++m)
+        if (mppi_status st = member_consts(&cfgs[m], m, true, h, consts[m]); st != MPPI_OK) { mppi_destroy(h); return st; }
+    h->batch = n;
     h->fuse_step = 0; // the two launches, always
-    if (mppi_status st = body(); st != MPPI_OK) { g_create_err = h->err; mppi_destroy(h); return st; }
+    if (mppi_status st = allocate_handle(h, cfg, n, consts.data()); st != MPPI_OK) { g_create_err = h->err; mppi_destroy(h); return st; }
     *out = h;
     return MPPI_OK;
 }
@@ -2120,13 +2187,7 @@ extern "C" mppi_status mppi_batch_set_goals(mppi_handle *h, const float *goals, 
 {
     MPPI_BATCH_ONLY(h);
     if (!goals || n != h->batch * h->s) return fail(h, MPPI_ERR_INVALID_ARG, "goals must hold n * s_dim floats");
-    MPPI_ENTER(h);
-    // into each member's constants (dC + m), the one copy the kernels read; hc mirrors member 0's
-    const size_t row = sizeof(float) * h->s;
-    HIP_TRY(h, hipMemcpy2DAsync((char *)h->dC + offsetof(DevConsts, goal), sizeof(DevConsts), goals, row, row, h->batch, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int i = 0; i < h->s; ++i) h->hc.goal[i] = goals[i];
-    return MPPI_OK;
+    return set_goals(h, goals);
 }
 
 extern "C" mppi_status mppi_batch_next(mppi_handle *h, const float *x, int n_x, float *u_out, int n_u)
@@ -2153,24 +2214,14 @@ extern "C" mppi_status mppi_batch_get_action_sequences(mppi_handle *h, float *U,
 {
     MPPI_BATCH_ONLY(h);
     if (!U || n != h->batch * h->HA) return fail(h, MPPI_ERR_INVALID_ARG, "U must hold n * tau * a_dim floats");
-    MPPI_ENTER(h);
-    const size_t row = sizeof(float) * h->HA, pitch = sizeof(float) * (h->HA + h->a);
-    HIP_TRY(h, hipMemcpy2DAsync(U, row, h->U_cur(), pitch, row, h->batch, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return MPPI_OK;
+    return get_sequences(h, U);
 }
 
 extern "C" mppi_status mppi_batch_set_action_sequences(mppi_handle *h, const float *U, int n)
 {
     MPPI_BATCH_ONLY(h);
     if (!U || n != h->batch * h->HA) return fail(h, MPPI_ERR_INVALID_ARG, "U must hold n * tau * a_dim floats");
-    MPPI_ENTER(h);
-    const size_t row = sizeof(float) * h->HA, pitch = sizeof(float) * (h->HA + h->a);
-    for (int i = 0; i < 2; ++i) HIP_TRY(h, hipMemsetAsync(h->d_Ubuf[i], 0, pitch * h->batch, h->stream)); // zero tails
-    h->u_cur = 0; h->u_off = 0; h->d_Uupd = nullptr;
-    HIP_TRY(h, hipMemcpy2DAsync(h->d_Ubuf[0], pitch, U, row, row, h->batch, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return MPPI_OK;
+    return set_sequences(h, U);
 }
 
 extern "C" mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what, float *out, size_t n)
@@ -2178,57 +2229,5 @@ extern "C" mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what
     MPPI_BATCH_ONLY(h);
     if (!out) return fail(h, MPPI_ERR_INVALID_ARG, "out is NULL");
     if (member < 0 || member >= h->batch) return fail(h, MPPI_ERR_INVALID_ARG, "member out of range");
-    MPPI_ENTER(h);
-    const size_t K = (size_t)h->K_local;
-    const float *src = nullptr;
-    size_t need = 0;
-    float *tmp = nullptr;
-    float *dbg = h->d_dbg + 8 * (size_t)member;
-    switch (what) {
-    case MPPI_DBG_COSTS: src = h->d_cost + K * member; need = K; break;
-    case MPPI_DBG_BETA: src = dbg; need = 1; break;
-    case MPPI_DBG_ETA: src = dbg + 1; need = 1; break;
-    case MPPI_DBG_AUX: src = dbg; need = 8; break;
-    case MPPI_DBG_U_UPDATED:
-        if (!h->d_Uupd) return fail(h, MPPI_ERR_INVALID_ARG, "no step has run since the action sequences were set");
-        src = h->d_Uupd + (size_t)(h->HA + h->a) * member; need = (size_t)h->HA; break;
-    case MPPI_DBG_WEIGHTS: {
-        need = K;
-        if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
-        HIP_TRY(h, hipMalloc((void **)&tmp, sizeof(float) * K));
-        hipLaunchKernelGGL(k_weights, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, (const DevConsts *)(h->dC + member), (const float *)(h->d_cost + K * member),
-                           (int)K, (const float *)dbg, (float *)nullptr, (float *)nullptr, tmp, (const float *)nullptr);
-        src = tmp;
-        break;
-    }
-    case MPPI_DBG_NOISE: {
-        // the member's noise of the LAST step, regenerated from its Philox key and Sigma at the previous step counter by the noise-only pass of
-        // the tile kernel (the point mass) or of k_rollout_gen (the AUV), as mppi_debug_get; that launch reads the member's constants (dC + m)
-        need = K * (size_t)h->HA;
-        if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
-        if (mppi_status s = ensure_eps(h); s != MPPI_OK) return s;
-        unsigned long long cur = 0;
-        HIP_TRY(h, hipMemcpyAsync(&cur, h->d_step, sizeof(cur), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (cur == 0) return fail(h, MPPI_ERR_INVALID_ARG, "no step has run yet");
-        const unsigned long long prev = cur - 1;
-        HIP_TRY(h, hipMemcpyAsync(h->d_step, &prev, sizeof(prev), hipMemcpyHostToDevice, h->stream));
-        DevConsts *const own = h->dC;
-        h->dC = own + member;
-        const hipError_t le = h->is_gen ? mppi_launch_gen(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps)
-                                        : launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
-        h->dC = own;
-        HIP_TRY(h, hipMemcpyAsync(h->d_step, &cur, sizeof(cur), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, le);
-        src = h->d_eps;
-        break;
-    }
-    default: return fail(h, MPPI_ERR_INVALID_ARG, "unknown debug item");
-    }
-    if (n != need) { if (tmp) (void)hipFree(tmp); return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size"); }
-    hipError_t e = hipMemcpyAsync(out, src, sizeof(float) * need, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (tmp) (void)hipFree(tmp);
-    HIP_TRY(h, e);
-    return MPPI_OK;
+    return debug_get(h, member, what, out, n);
 }

@@ -127,16 +127,19 @@ struct mppi_handle {
     unsigned long long pre_step = 0; // host mirror of the Philox step counter
     unsigned long long pre_count = 0; // launches since the mode was entered (parity = stream)
     unsigned next_seq() { step_seq = (step_seq + 1u) & 0x7fffffffu; if (step_seq == 0u) step_seq = 1u; return step_seq; }
-    // a batched handle (mppi_create_batch_configs): `batch` controllers sharing this geometry, stepped together (mppi_launch_batch.hip; the
-    // Fossen AUV model: mppi_launch_batch_gen.hip). hc is member 0's constants.
-    // Per member m: x at d_bx + m*s, U in d_Ubuf[i] + m*(HA + a) (each with its zero tail), costs at d_cost + m*K, records at
-    // d_part + m*nbp*(2 + HA), beta/eta at d_dbg + 8m, constants (Philox key, goal, lambda, gamma, upsilon, Sigma, Q) at dC + m.
-    // 0 = a plain handle.
+    // The host-side layout: a handle holds members(h) controllers that share this geometry, and a lone handle is the one-member case.
+    // Member m's x is at d_bx + m*s (a batch's staging), its U in d_Ubuf[i] + m*(HA + a) (the sequence and its zero tail), its costs at
+    // d_cost + m*K_local, its records at d_part + m*nbp*(2 + HA), beta/eta/aux at d_dbg + 8m, its constants (Philox key, goal, lambda, gamma,
+    // upsilon, Sigma, Q) at dC + m; hc is member 0's constants. Everything else exists once.
+    // batch = 0: a plain handle (mppi_create), on the lone kernels; batch = n >= 1: a batched handle (mppi_create_batch_configs), stepped by
+    // the two batched launches (mppi_launch_batch.hip; the Fossen AUV model: mppi_launch_batch_gen.hip).
     int batch = 0;
     float *d_bx = nullptr, *d_bu = nullptr;
     size_t xchg_step_slots() const { return (size_t)2 * HA * shard_count * 3; }
     size_t xchg_inbox_bytes() const { return sizeof(unsigned long long) * (xchg_step_slots() + (size_t)2 * shard_count); }
 };
+
+inline int members(const mppi_handle *h) { return h->batch ? h->batch : 1; }
 
 // The dynamic-LDS ceiling (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the (kernel instance, device) pair,
 // not to a handle: several handles, devices and host threads share one template instance. It is kept process-wide and

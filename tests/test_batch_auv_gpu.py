@@ -5,18 +5,16 @@ The contract (include/mppi_c.h): member m is BIT-IDENTICAL to a lone Handle made
 default k_rollout_auv_pc path, fed the same x, goal and action sequence on the same step counter: sample costs, U' and u; members never
 interact. Through that, every member inherits the lone handle's parity with the oracle; a direct oracle check is here as well.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from batch_util import (E3, Q10, auv_members as members, batch_with as _batch_with, batch_with_mlp as _batch_with_mlp, create_batch, lone,
+                        rexrov2)
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 U_TOL = 1e-5
-Q10 = np.diag([100.0] * 3 + [10.0] + [1.0] * 6) + 0.01
-E3 = dict(normal=[0.0, np.sin(0.3), np.cos(0.3)], aVec=[1.0, 0.0, 0.0], axis=[2.0, 1.5], speed=1.0, m_state=50.0, m_vel=5.0)
 
 
 @pytest.fixture(scope="module")
@@ -24,11 +22,6 @@ def m():
     import mppi_tf_amd
     assert mppi_tf_amd.load().mppi_device_count() >= 1, "no GPU visible to libmppi_hip.so"
     return mppi_tf_amd
-
-
-def rexrov2(rk=2):
-    from mppi_tf_amd.auv import auv_task
-    return dict(auv_task(8)["auv"], rk=rk)
 
 
 def config(K, H, cost="quadratic", rk=2, dense_sigma=False):
@@ -49,34 +42,6 @@ def config(K, H, cost="quadratic", rk=2, dense_sigma=False):
     else:
         d["ellipse3d"] = E3
     return d
-
-
-def members(B, H, seed=0):
-    """distinct x (unit quaternions), goals and initial sequences per member"""
-    rng = np.random.default_rng(200 + seed)
-    X = np.zeros((B, 13), F32)
-    X[:, :3] = rng.uniform(-1, 1, (B, 3))
-    q = rng.standard_normal((B, 4))
-    X[:, 3:7] = q / np.linalg.norm(q, axis=1, keepdims=True)
-    X[:, 7:] = rng.uniform(-0.3, 0.3, (B, 6))
-    G = np.zeros((B, 13), F32)
-    G[:, :3] = rng.uniform(-3, 3, (B, 3))
-    qg = rng.standard_normal((B, 4))
-    G[:, 3:7] = qg / np.linalg.norm(qg, axis=1, keepdims=True)
-    U0 = (50.0 * rng.standard_normal((B, H, 6))).astype(F32)
-    return X, G, U0
-
-
-def lone(m, c, seeds, G, U0, lim=None):
-    hs = []
-    for i, s in enumerate(seeds):
-        h = m.Handle(seed=s, goal=G[i], **c)
-        assert h.rollout_kernel_name().startswith("mppi::k_rollout_auv_pc<")
-        h.set_action_sequence(U0[i])
-        if lim:
-            h.set_action_limits(*lim)
-        hs.append(h)
-    return hs
 
 
 EQUIV = [(4, 4096, 40, "quadratic", 2, False), (3, 1000, 20, "quat", 4, False), (5, 3000, 16, "dense", 1, True),
@@ -208,18 +173,6 @@ def test_auv_debug_items_equal_lone_handles(m):
     hb.close()
 
 
-def _create_batch(n=2, **fields):
-    """mppi_create_batch on a raw 13-state mppi_config (K = 256, tau = 16) -> (status, handle)"""
-    from mppi_tf_amd import _lib
-    lib = _lib.load()
-    cfg = _lib.Config()
-    assert lib.mppi_config_init(C.byref(cfg), 256, 16, 0.1, 1.0, 13, 6) == 0
-    for k, v in fields.items():
-        setattr(cfg, k, v)
-    h = _lib._H()
-    return lib.mppi_create_batch(C.byref(cfg), n, None, C.byref(h)), h
-
-
 def test_auv_batch_refusals(m):
     from mppi_tf_amd import _lib
     lib = _lib.load()
@@ -230,7 +183,7 @@ def test_auv_batch_refusals(m):
         with pytest.raises(m.MppiError) as e:
             _batch_with_mlp(m, kw)
         assert e.value.status == UNSUP and word in str(e.value), str(e.value)
-    st, h = _create_batch(model_kind=_lib.MODEL_AUV)
+    st, h = create_batch(s_dim=13, a_dim=6, model_kind=_lib.MODEL_AUV)
     assert st == UNSUP and not h and "AUV" in lib.mppi_last_error(None).decode()
     with pytest.raises(m.MppiError) as e:
         _batch_with(m, normalize_cost=1)
@@ -248,40 +201,6 @@ def test_auv_batch_refusals(m):
     assert hb.rollout_kernel_name() == "mppi::k_rollout_auv_pc_batch<true>"
     hb.next(members(2, 16)[0])  # still serves its own steps
     hb.close()
-
-
-def _batch_with_mlp(m, kw):
-    """a batch of a learned 13-state model through the Python binding's config path (Handle's keywords on a raw mppi_create_batch)"""
-    from mppi_tf_amd import _lib
-    lib = _lib.load()
-    cfg = _lib.Config()
-    assert lib.mppi_config_init(C.byref(cfg), 256, 16, 0.1, 1.0, 13, 6) == 0
-    name, mlp = next(iter(kw.items()))
-    desc, held = _lib._mlp_desc(mlp, 15 if name == "nnauv_speed" else 16, 6 if name == "nnauv_speed" else 13)
-    cfg.model_kind = _lib.MODEL_NN_AUV_SPEED if name == "nnauv_speed" else _lib.MODEL_NN_AUV
-    cfg.mlp = C.pointer(desc)
-    h = _lib._H()
-    st = lib.mppi_create_batch(C.byref(cfg), 2, None, C.byref(h))
-    if st != _lib.OK:
-        raise m.MppiError(st, lib.mppi_last_error(None).decode())
-    lib.mppi_destroy(h)
-
-
-def _batch_with(m, **fields):
-    """an AUV batch (rexrov2) with raw config fields set on top"""
-    from mppi_tf_amd import _lib
-    lib = _lib.load()
-    cfg = _lib.Config()
-    assert lib.mppi_config_init(C.byref(cfg), 256, 16, 0.1, 1.0, 13, 6) == 0
-    keep = []
-    _lib._fill_13state(cfg, keep, rexrov2(), False, None, None)
-    for k, v in fields.items():
-        setattr(cfg, k, v)
-    h = _lib._H()
-    st = lib.mppi_create_batch(C.byref(cfg), 2, None, C.byref(h))
-    if st != _lib.OK:
-        raise m.MppiError(st, lib.mppi_last_error(None).decode())
-    lib.mppi_destroy(h)
 
 
 def test_auv_closed_loop_equals_lone_handles(m):

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from batch_util import create_batch, plant, pm_members as members
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -24,14 +25,6 @@ def m():
     return mppi_tf_amd
 
 
-def plant(x, u, a, dt=0.1):
-    x = x.copy()
-    for j in range(a):
-        x[2 * j] = x[2 * j] + F32(dt) * x[2 * j + 1] + F32(dt * dt / 2) * u[j]
-        x[2 * j + 1] = x[2 * j + 1] + F32(dt) * u[j]
-    return x
-
-
 def common(K, H, a, dense=False):
     s = 2 * a
     d = dict(k=K, tau=H, s_dim=s, a_dim=a, dt=0.1, mass=1.0, lam=1.0, sigma=np.eye(a) * 0.25, Q=np.ones(s))
@@ -42,17 +35,6 @@ def common(K, H, a, dense=False):
         S = rng.uniform(-0.05, 0.05, (a, a))
         d["sigma"] = (0.25 * np.eye(a) + (S + S.T) / 2).astype(F32)
     return d
-
-
-def members(B, a, H, seed=0):
-    """distinct x, goal and initial U per member"""
-    rng = np.random.default_rng(100 + seed)
-    s = 2 * a
-    X = rng.uniform(-1, 1, (B, s)).astype(F32)
-    G = np.zeros((B, s), F32)
-    G[:, 0::2] = rng.uniform(-1, 1, (B, a))
-    U0 = rng.uniform(-0.2, 0.2, (B, H, a)).astype(F32)
-    return X, G, U0
 
 
 EQUIV = [(4, 4096, 64, 2, False), (5, 3000, 50, 2, False), (3, 1000, 20, 1, False), (16, 4096, 64, 3, False), (2, 65536, 64, 3, False),
@@ -174,19 +156,6 @@ def test_device_path_equals_host_path(m):
     hd.close(); hh.close()
 
 
-def _create_batch(m, n=2, **fields):
-    """mppi_create_batch on a raw mppi_config (K = 256, tau = 16, point mass a = 2 unless `fields` say otherwise) -> (status, handle)"""
-    from mppi_tf_amd import _lib
-    lib = _lib.load()
-    cfg = _lib.Config()
-    assert lib.mppi_config_init(C.byref(cfg), 256, 16, 0.1, 1.0, fields.pop("s_dim", 4), fields.pop("a_dim", 2)) == 0
-    for k, v in fields.items():
-        setattr(cfg, k, v)
-    h = _lib._H()
-    st = lib.mppi_create_batch(C.byref(cfg), n, None, C.byref(h))
-    return st, h
-
-
 def test_refusals(m):
     from mppi_tf_amd import _lib
     lib = _lib.load()
@@ -198,10 +167,10 @@ def test_refusals(m):
                          (dict(state_cost_kind=_lib.STATE_COST_ELLIPSE), "ellipse"), (dict(state_cost_kind=_lib.STATE_COST_ELLIPSE3D, s_dim=13, a_dim=6), "ellipse"),
                          (dict(state_cost_kind=_lib.STATE_COST_QUAT, s_dim=13, a_dim=6), "StaticQuatCost"), (dict(normalize_cost=1), "normalize_cost"),
                          (dict(flags=4), "FP_CONTRACT"), (dict(flags=2), "BF16X3"), (dict(shard_count=2), "shard")]:
-        st, h = _create_batch(m, **fields)
+        st, h = create_batch(**fields)
         assert st == UNSUP and not h, fields
         assert word in lib.mppi_last_error(None).decode(), (fields, lib.mppi_last_error(None))
-    st, h = _create_batch(m, n=0)
+    st, h = create_batch(n=0)
     assert st == INVAL and not h
     hb = m.BatchHandle(n=3, k=256, tau=16, s_dim=4, a_dim=2)
     assert lib.mppi_batch_size(hb.h) == 3

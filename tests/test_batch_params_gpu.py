@@ -12,11 +12,12 @@ import sys
 import numpy as np
 import pytest
 
+from batch_util import (E3, Q10, assert_members_equal, auv_members, close, create_batch_configs as _create, make, plant, pm_members, ptr as _ptr,
+                        raw_configs as _cfgs)
+
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-Q10 = np.diag([100.0] * 3 + [10.0] + [1.0] * 6) + 0.01
-E3 = dict(normal=[0.0, np.sin(0.3), np.cos(0.3)], aVec=[1.0, 0.0, 0.0], axis=[2.0, 1.5], speed=1.0, m_state=50.0, m_vel=5.0)
 
 
 @pytest.fixture(scope="module")
@@ -24,14 +25,6 @@ def m():
     import mppi_tf_amd
     assert mppi_tf_amd.load().mppi_device_count() >= 1, "no GPU visible to libmppi_hip.so"
     return mppi_tf_amd
-
-
-def plant(x, u, a, dt=0.1):
-    x = x.copy()
-    for j in range(a):
-        x[2 * j] = x[2 * j] + F32(dt) * x[2 * j + 1] + F32(dt * dt / 2) * u[j]
-        x[2 * j + 1] = x[2 * j + 1] + F32(dt) * u[j]
-    return x
 
 
 def spd(rng, n, scale, off):
@@ -82,57 +75,6 @@ def auv_sweep(B, K, H, cost, rk, seed=0):
     names = dict(lams="lam", sigmas="sigma", Qs="Q")
     lone = [dict(shared, **{names[k]: v[i] for k, v in per.items()}) for i in range(B)]
     return shared, per, lone
-
-
-def pm_members(B, a, H, seed=0):
-    rng = np.random.default_rng(100 + seed)
-    X = rng.uniform(-1, 1, (B, 2 * a)).astype(F32)
-    G = np.zeros((B, 2 * a), F32)
-    G[:, 0::2] = rng.uniform(-1, 1, (B, a))
-    return X, G, rng.uniform(-0.2, 0.2, (B, H, a)).astype(F32)
-
-
-def auv_members(B, H, seed=0):
-    rng = np.random.default_rng(200 + seed)
-    X = np.zeros((B, 13), F32)
-    X[:, :3] = rng.uniform(-1, 1, (B, 3))
-    q = rng.standard_normal((B, 4))
-    X[:, 3:7] = q / np.linalg.norm(q, axis=1, keepdims=True)
-    X[:, 7:] = rng.uniform(-0.3, 0.3, (B, 6))
-    G = np.zeros((B, 13), F32)
-    G[:, :3] = rng.uniform(-3, 3, (B, 3))
-    qg = rng.standard_normal((B, 4))
-    G[:, 3:7] = qg / np.linalg.norm(qg, axis=1, keepdims=True)
-    return X, G, (50.0 * rng.standard_normal((B, H, 6))).astype(F32)
-
-
-def make(m, shared, per, lone_kw, seeds, G, U0, lone_prefix):
-    hb = m.BatchHandle(n=len(seeds), seeds=seeds, goals=G, **shared, **per)
-    hb.set_action_sequences(U0)
-    hs = []
-    for i, kw in enumerate(lone_kw):
-        h = m.Handle(seed=seeds[i], **dict(kw, goal=G[i]))
-        assert h.rollout_kernel_name().startswith(lone_prefix), h.rollout_kernel_name()
-        h.set_action_sequence(U0[i])
-        hs.append(h)
-    return hb, hs
-
-
-def assert_members_equal(m, hb, hs, ub, us, tag):
-    Ub = hb.get_action_sequences()
-    for i, h in enumerate(hs):
-        msg = "member %d %s" % (i, tag)
-        np.testing.assert_array_equal(hb.debug_get(i, m.DBG_COSTS), h.debug_get(m.DBG_COSTS), err_msg=msg)
-        np.testing.assert_array_equal(hb.debug_get(i, m.DBG_BETA), h.debug_get(m.DBG_BETA), err_msg=msg)
-        np.testing.assert_array_equal(hb.debug_get(i, m.DBG_ETA), h.debug_get(m.DBG_ETA), err_msg=msg)
-        np.testing.assert_array_equal(ub[i], us[i], err_msg=msg)
-        np.testing.assert_array_equal(Ub[i], h.get_action_sequence(), err_msg=msg)
-
-
-def close(hb, hs):
-    for h in hs:
-        h.close()
-    hb.close()
 
 
 # (B, K, H, a, dense_sigma, dense_q, py, upsilon_scales_noise, the lone handle's kernel)
@@ -265,36 +207,6 @@ def test_debug_items_are_the_members_own(m, model):
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------------------
-def _cfgs(n, s_dim=4, a_dim=2, k=256, tau=16, each=None, **fields):
-    """n raw mppi_configs (point mass a = 2 unless `fields` say otherwise); each(m, cfg, keep) edits member m -> (array, keep)"""
-    from mppi_tf_amd import _lib
-    lib = _lib.load()
-    arr, keep = (_lib.Config * n)(), []
-    for i in range(n):
-        assert lib.mppi_config_init(C.byref(arr[i]), k, tau, 0.1, 1.0, s_dim, a_dim) == 0
-        for key, v in fields.items():
-            setattr(arr[i], key, v)
-        if each:
-            each(i, arr[i], keep)
-    return arr, keep
-
-
-def _create(arr, n=None):
-    from mppi_tf_amd import _lib
-    lib = _lib.load()
-    h = _lib._H()
-    st = lib.mppi_create_batch_configs(arr, len(arr) if n is None else n, C.byref(h))
-    if h:
-        lib.mppi_destroy(h)
-    return st, lib.mppi_last_error(None).decode(), bool(h)
-
-
-def _ptr(keep, a):
-    from mppi_tf_amd import _lib
-    keep.append(np.ascontiguousarray(a, F32).ravel())
-    return keep[-1].ctypes.data_as(_lib.FP)
-
-
 def test_refusals(m):
     from mppi_tf_amd import _lib
     lib = _lib.load()
@@ -371,6 +283,48 @@ def test_refusals(m):
         with pytest.raises(m.MppiError) as e:
             m.BatchHandle(n=3, k=256, tau=16, s_dim=4, a_dim=2, **kw)
         assert e.value.status == INVAL, kw
+
+
+def test_singular_member_after_member_zero_then_repaired(m):
+    """K = 256, H = 16, a = 2, n = 3 through mppi_create_batch_configs. Member 2's singular Sigma is found after member 0 passed every
+    check, where the batch's one allocation follows: MPPI_ERR_SINGULAR_SIGMA naming member 2, no handle. The same configs with that Sigma
+    repaired create, step once and equal the three lone handles mppi_create(&cfgs[i]) bit for bit (u, U', costs, beta, eta)."""
+    from mppi_tf_amd import _lib
+    lib = _lib.load()
+    n, K, H, a = 3, 256, 16, 2
+    sig = [np.diag([0.2, 0.3]), np.diag([0.4, 0.25]), np.diag([0.15, 0.5])]
+
+    def each(bad):
+        def f(i, c, kp):
+            c.sigma, c.lam, c.seed = _ptr(kp, np.zeros((a, a)) if (bad and i == 2) else sig[i]), 0.5 * (i + 1), 31 + i
+        return f
+    arr, keep = _cfgs(n, 2 * a, a, K, H, each=each(True))
+    hb = _lib._H()
+    st = lib.mppi_create_batch_configs(arr, n, C.byref(hb))
+    msg = lib.mppi_last_error(None).decode()
+    assert st == _lib.ERR_SINGULAR_SIGMA and "member 2" in msg and "sigma is singular" in msg and not hb, (st, msg)
+    arr, keep = _cfgs(n, 2 * a, a, K, H, each=each(False))
+    assert lib.mppi_create_batch_configs(arr, n, C.byref(hb)) == 0 and hb, lib.mppi_last_error(None)
+    assert lib.mppi_batch_size(hb) == n
+    X = np.random.default_rng(12).uniform(-1, 1, (n, 2 * a)).astype(F32)
+    fp = lambda x: x.ctypes.data_as(_lib.FP)
+    ub, Ub = np.zeros((n, a), F32), np.zeros((n, H, a), F32)
+    assert lib.mppi_batch_next(hb, fp(X), X.size, fp(ub), ub.size) == 0, lib.mppi_last_error(hb)
+    assert lib.mppi_batch_get_action_sequences(hb, fp(Ub), Ub.size) == 0
+    for i in range(n):
+        h = _lib._H()
+        assert lib.mppi_create(C.byref(arr[i]), C.byref(h)) == 0, lib.mppi_last_error(None)
+        u, U = np.zeros(a, F32), np.zeros((H, a), F32)
+        assert lib.mppi_next(h, fp(X[i]), 2 * a, fp(u), a) == 0 and lib.mppi_get_action_sequence(h, fp(U), U.size) == 0
+        np.testing.assert_array_equal(ub[i], u, err_msg="member %d" % i)
+        np.testing.assert_array_equal(Ub[i], U, err_msg="member %d" % i)
+        for what, size in ((m.DBG_COSTS, K), (m.DBG_BETA, 1), (m.DBG_ETA, 1)):
+            cb, cl = np.zeros(size, F32), np.zeros(size, F32)
+            assert lib.mppi_batch_debug_get(hb, i, what, fp(cb), size) == 0 and lib.mppi_debug_get(h, what, fp(cl), size) == 0
+            np.testing.assert_array_equal(cb, cl, err_msg="member %d item %d" % (i, what))
+        lib.mppi_destroy(h)
+    assert len({tuple(r) for r in ub}) == n  # the members' controls differ
+    lib.mppi_destroy(hb)
 
 
 # ---- device path, closed loop, the example ------------------------------------------------------------------------------------------

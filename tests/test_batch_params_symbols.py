@@ -89,6 +89,41 @@ def test_config_builder_differs_only_in_the_per_member_fields(pkg):
     assert {k for k in c0 if c0[k] != c1[k]} == {"lam", "Q", "seed"}
 
 
+def test_lone_and_batch_configs_come_from_one_filler(pkg, monkeypatch):
+    """For the same shared keywords, the config Handle.__init__ passes to mppi_create and member 0 of batch_configs(...) have equal
+    contents: both come from _fill_config. mppi_create is replaced by a recorder that answers MPPI_ERR_NO_DEVICE (no GPU is used)."""
+    from mppi_tf_amd import _lib
+    from mppi_tf_amd.auv import auv_task
+    lib, seen = _lib.load(), []
+
+    def recorder(s, a):
+        def create(cfg, out):
+            seen.append(_contents(cfg._obj, s, a))
+            return _lib.ERR_NO_DEVICE
+        return create
+    rng = np.random.default_rng(3)
+    L = rng.uniform(-0.3, 0.3, (6, 6)) + np.eye(6)
+    t = auv_task(8)
+    cases = [(6, 3, dict(k=4096, tau=64, s_dim=6, a_dim=3, dt=0.05, mass=2.0, lam=0.3, gamma=0.5, upsilon=1.5, sigma=np.diag([0.1, 0.2, 0.3]),
+                         goal=np.arange(6), Q=(L @ L.T).astype(np.float32), action_cost=_lib.ACTION_COST_PY, upsilon_scales_noise=True, seed=7)),
+             (13, 6, dict(k=1024, tau=8, s_dim=13, a_dim=6, dt=0.1, lam=0.5, sigma=t["sigma"], Q=t["Q"], auv=t["auv"], seed=5))]
+    for s, a, kw in cases:
+        monkeypatch.setattr(lib, "mppi_create", recorder(s, a))
+        with pytest.raises(_lib.MppiError) as e:
+            _lib.Handle(**kw)
+        assert e.value.status == _lib.ERR_NO_DEVICE
+        monkeypatch.undo()
+        lone = seen.pop()
+        assert not seen
+        keep = []
+        assert _contents(_lib._fill_config(lib, keep, **kw), s, a) == lone  # the filler, called on its own
+        cfgs, keep = _lib.batch_configs(2, **kw)
+        assert _contents(cfgs[0], s, a) == lone
+        assert lone["sigma"] is not None and lone["Q"] is not None and lone["seed"] == kw["seed"]
+    assert lone["model_kind"] == _lib.MODEL_AUV and lone["auv"] is not None
+    assert not hasattr(_lib, "_batch_config")
+
+
 def test_config_builder_checks_the_list_lengths(pkg):
     from mppi_tf_amd import _lib
     for kw in (dict(lams=[1.0]), dict(gammas=[1.0] * 3), dict(upsilons=[]), dict(sigmas=[np.eye(2)] * 3), dict(Qs=[np.ones(4)]),

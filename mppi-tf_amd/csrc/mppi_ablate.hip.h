@@ -16,13 +16,13 @@
 #define MPPI_ABL_STANDIN_(z, n, gk, grp) \
     _Pragma("unroll") for (int j_ = 0; j_ < (n); ++j_) (z)[j_] = (float)((int)(((gk) * 2654435761ull + (grp) * 40503ull + j_) & 1023) - 512) * (1.0f / 512.0f)
 #define MPPI_NORMALS_GROUP(A, seed, gk, grp, z) MPPI_ABL_STANDIN_(z, 4 * (A), gk, grp)
-#define MPPI_NORMALS_GROUP_UB(A, seed, gk, grp, z) MPPI_ABL_STANDIN_(z, 4 * (A), gk, grp)
+#define MPPI_NORMALS_GROUP_UB(A, seed, gk, lane_consts, grp, z) MPPI_ABL_STANDIN_(z, 4 * (A), gk, grp)
 #elif defined(MPPI_PHILOX_BLOCK_MAJOR) // A/B: the Philox blocks of a group one after the other (r03) instead of round-major (r04)
 #define MPPI_NORMALS_GROUP(A, seed, gk, grp, z) normals_group<A>(seed, gk, grp, z)
-#define MPPI_NORMALS_GROUP_UB(A, seed, gk, grp, z) normals_group_ub_block_major<A>(seed, gk, grp, z)
+#define MPPI_NORMALS_GROUP_UB(A, seed, gk, lane_consts, grp, z) normals_group_ub_block_major<A>(seed, gk, grp, z)
 #else
 #define MPPI_NORMALS_GROUP(A, seed, gk, grp, z) normals_group<A>(seed, gk, grp, z)
-#define MPPI_NORMALS_GROUP_UB(A, seed, gk, grp, z) normals_group_ub<A>(seed, gk, grp, z)
+#define MPPI_NORMALS_GROUP_UB(A, seed, gk, lane_consts, grp, z) normals_group_ub<A>(seed, gk, lane_consts, grp, z)
 #endif
 
 // ---- recurrence length -----------------------------------------------------------------------------------------------------

@@ -274,6 +274,123 @@ __device__ __forceinline__ void philox4x32_10_blocks_ub(unsigned long long seed,
     for (int q = 0; q < A; ++q) out[q] = uint4{c0[q], c1[q], c2[q], c3[q]};
 }
 
+// What philox4x32_10_blocks_ub computes again for every group although it is the same for every block a lane draws in one launch: round 0's
+// M1 * sample (the counter's third word), and — while the HIGH word of the block index is the same for every block of the launch, which it is
+// except in the one control step in ~2^32 / (groups * A) whose blocks straddle a multiple of 2^32 — round 0's a0 = hi(M1 * sample) ^ hi(block) ^ k0
+// and with it round 1's M0 * a0: its high word, its low word b3, and b3 ^ k1 of round 2. Built once in front of the producers' horizon loop
+// (make_philox_lane): 4 of a group's 52 products and 3 xors go, and round 2's three-input xors become two-input ones. `uniform_hi` (wave-uniform)
+// says whether the block-independent half holds; a group of a launch where it does not takes philox4x32_10_blocks_rolled.
+struct PhiloxLane {
+    unsigned int m1_lo, m1_hi; // M1 * sample
+    unsigned int m0_hi;        // hi(M0 * a0)
+    unsigned int b3, b3k1;     // lo(M0 * a0), and xor-ed with round 2's k1
+    bool uniform_hi;
+};
+// first_block .. last_block: every Philox block index of the launch (wave-uniform)
+__device__ __forceinline__ PhiloxLane make_philox_lane(unsigned long long seed, unsigned int subsequence_lo, unsigned long long first_block,
+                                                       unsigned long long last_block)
+{
+    PhiloxLane L;
+    const unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
+    const unsigned int c1s = (unsigned int)(first_block >> 32);
+    const unsigned long long m1 = (unsigned long long)ROCRAND_PHILOX_M4x32_1 * subsequence_lo;
+    L.m1_lo = (unsigned int)m1; L.m1_hi = (unsigned int)(m1 >> 32);
+    const unsigned long long m0 = (unsigned long long)ROCRAND_PHILOX_M4x32_0 * (L.m1_hi ^ (c1s ^ k0));
+    L.m0_hi = (unsigned int)(m0 >> 32); L.b3 = (unsigned int)m0;
+    L.b3k1 = L.b3 ^ (k1 + 2u * ROCRAND_PHILOX_W32_1);
+    L.uniform_hi = c1s == (unsigned int)(last_block >> 32);
+    return L;
+}
+
+// philox4x32_10_blocks_ub with the lane's constants (L.uniform_hi must hold): the same integer arithmetic per block, regrouped — bit-identical.
+template <int A>
+__device__ __forceinline__ void philox4x32_10_blocks_lane(unsigned long long seed, const PhiloxLane &L, unsigned long long block0_uniform, uint4 (&out)[A])
+{
+    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
+    unsigned int c0[A], c1[A], c2[A], c3[A];
+    // round 0: what depends on the block is uniform — M0 * lo(block)
+    unsigned int a2s[A], a3s[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+        const unsigned int c0s = (unsigned int)(block0_uniform + (unsigned long long)q);
+        const unsigned long long m0s = (unsigned long long)ROCRAND_PHILOX_M4x32_0 * c0s; // scalar
+        a2s[q] = (unsigned int)(m0s >> 32) ^ k1; a3s[q] = (unsigned int)m0s;
+    }
+    k0 += ROCRAND_PHILOX_W32_0; k1 += ROCRAND_PHILOX_W32_1;
+    // round 1: M1 * a2s on the scalar unit, M0 * a0 from L
+    unsigned int b0[A], b1s[A], b2[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+        const unsigned long long m1s = (unsigned long long)ROCRAND_PHILOX_M4x32_1 * a2s[q];   // scalar
+        b0[q] = L.m1_lo ^ ((unsigned int)(m1s >> 32) ^ k0); b1s[q] = (unsigned int)m1s;
+        b2[q] = L.m0_hi ^ (a3s[q] ^ k1);
+    }
+    k0 += ROCRAND_PHILOX_W32_0; k1 += ROCRAND_PHILOX_W32_1;
+    // round 2: c1 = b1s uniform, c3 = L.b3 the lane's
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+        const unsigned long long m0 = (unsigned long long)ROCRAND_PHILOX_M4x32_0 * b0[q];
+        const unsigned long long m1b = (unsigned long long)ROCRAND_PHILOX_M4x32_1 * b2[q];
+        c0[q] = (unsigned int)(m1b >> 32) ^ (b1s[q] ^ k0); c1[q] = (unsigned int)m1b;
+        c2[q] = (unsigned int)(m0 >> 32) ^ L.b3k1; c3[q] = (unsigned int)m0;
+    }
+    k0 += ROCRAND_PHILOX_W32_0; k1 += ROCRAND_PHILOX_W32_1;
+#pragma unroll
+    for (int r = 3; r < 10; ++r) {
+        unsigned long long p0[A], p1[A];
+#pragma unroll
+        for (int q = 0; q < A; ++q) {
+            p0[q] = (unsigned long long)ROCRAND_PHILOX_M4x32_0 * c0[q];
+            p1[q] = (unsigned long long)ROCRAND_PHILOX_M4x32_1 * c2[q];
+        }
+#pragma unroll
+        for (int q = 0; q < A; ++q) {
+            const unsigned int n0 = __builtin_amdgcn_bitop3_b32((unsigned int)(p1[q] >> 32), c1[q], k0, 0x96);
+            const unsigned int n2 = __builtin_amdgcn_bitop3_b32((unsigned int)(p0[q] >> 32), c3[q], k1, 0x96);
+            c0[q] = n0; c1[q] = (unsigned int)p1[q]; c2[q] = n2; c3[q] = (unsigned int)p0[q];
+        }
+        k0 += ROCRAND_PHILOX_W32_0; k1 += ROCRAND_PHILOX_W32_1;
+#if !defined(MPPI_PHILOX_FREE_ORDER)
+        // round-major, pinned as in philox4x32_10_blocks_ub
+        if constexpr (A == 2) asm volatile("" : "+v"(c0[0]), "+v"(c2[0]), "+v"(c0[1]), "+v"(c2[1]));
+        if constexpr (A == 3) asm volatile("" : "+v"(c0[0]), "+v"(c2[0]), "+v"(c0[1]), "+v"(c2[1]), "+v"(c0[2]), "+v"(c2[2]));
+        if constexpr (A == 4) asm volatile("" : "+v"(c0[0]), "+v"(c2[0]), "+v"(c0[1]), "+v"(c2[1]), "+v"(c0[2]), "+v"(c2[2]), "+v"(c0[3]), "+v"(c2[3]));
+#endif
+    }
+#pragma unroll
+    for (int q = 0; q < A; ++q) out[q] = uint4{c0[q], c1[q], c2[q], c3[q]};
+}
+
+// The same A blocks where the lane's constants do not hold (the launch whose blocks straddle a multiple of 2^32): the plain block function
+// (philox4x32_10_block) for the A blocks, its ten rounds a ROLLED loop — this path runs in one control step in tens of millions and sits in
+// every group of the unrolled horizon loop, so it is written for size, not speed.
+template <int A>
+__device__ __forceinline__ void philox4x32_10_blocks_rolled(unsigned long long seed, unsigned int subsequence_lo, unsigned long long block0_uniform,
+                                                            uint4 (&out)[A])
+{
+    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
+    unsigned int c0[A], c1[A], c2[A], c3[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+        const unsigned long long blk = block0_uniform + (unsigned long long)q;
+        c0[q] = (unsigned int)blk; c1[q] = (unsigned int)(blk >> 32); c2[q] = subsequence_lo; c3[q] = 0u;
+    }
+#pragma clang loop unroll(disable)
+    for (int r = 0; r < 10; ++r) {
+#pragma unroll
+        for (int q = 0; q < A; ++q) {
+            const unsigned long long m0 = (unsigned long long)ROCRAND_PHILOX_M4x32_0 * c0[q];
+            const unsigned long long m1 = (unsigned long long)ROCRAND_PHILOX_M4x32_1 * c2[q];
+            const unsigned int n0 = (unsigned int)(m1 >> 32) ^ c1[q] ^ k0;
+            const unsigned int n2 = (unsigned int)(m0 >> 32) ^ c3[q] ^ k1;
+            c0[q] = n0; c1[q] = (unsigned int)m1; c2[q] = n2; c3[q] = (unsigned int)m0;
+        }
+        k0 += ROCRAND_PHILOX_W32_0; k1 += ROCRAND_PHILOX_W32_1;
+    }
+#pragma unroll
+    for (int q = 0; q < A; ++q) out[q] = uint4{c0[q], c1[q], c2[q], c3[q]};
+}
+
 // The 4 standard normals of ONE Philox block of a sample (block uniform or not): the single place every rollout kernel that
 // draws block by block (k_rollout_mlp2, k_rollout_mlp32, k_rollout_nnauv32) gets them from, so that the rollout and the tile
 // record (mlp_tile_record -> normals_group) always agree — also in the -DMPPI_ROCRAND_NORMALS variant build.
@@ -316,6 +433,27 @@ __device__ __forceinline__ void normals_group_ub(unsigned long long seed, unsign
 #else
     uint4 r[A];
     philox4x32_10_blocks_ub<A>(seed, gk_lo, group_index_uniform * A, r);
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+        const float2 n0 = box_muller_hw(r[q].x, r[q].y), n1 = box_muller_hw(r[q].z, r[q].w);
+        z[4 * q + 0] = n0.x; z[4 * q + 1] = n0.y; z[4 * q + 2] = n1.x; z[4 * q + 3] = n1.y;
+    }
+#endif
+}
+
+// ... and with the lane's constants L = make_philox_lane(seed, gk_lo, the launch's first and last block): the producers' call. The test of
+// L.uniform_hi sits in front of the group's Philox rounds, where the group's body begins anyway (nothing is scheduled across it).
+// -DMPPI_PHILOX_NO_LANE_CONSTS (A/B timing, tools/ablate.py): every group computes everything, as before.
+template <int A>
+__device__ __forceinline__ void normals_group_ub(unsigned long long seed, unsigned int gk_lo, const PhiloxLane &L, unsigned long long group_index_uniform,
+                                                 float (&z)[4 * A])
+{
+#if defined(MPPI_ROCRAND_NORMALS) || defined(MPPI_PHILOX_NO_LANE_CONSTS)
+    normals_group_ub<A>(seed, gk_lo, group_index_uniform, z);
+#else
+    uint4 r[A];
+    if (__builtin_expect(L.uniform_hi, 1)) philox4x32_10_blocks_lane<A>(seed, L, group_index_uniform * A, r);
+    else philox4x32_10_blocks_rolled<A>(seed, gk_lo, group_index_uniform * A, r);
 #pragma unroll
     for (int q = 0; q < A; ++q) {
         const float2 n0 = box_muller_hw(r[q].x, r[q].y), n1 = box_muller_hw(r[q].z, r[q].w);

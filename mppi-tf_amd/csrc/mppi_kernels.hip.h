@@ -186,10 +186,42 @@ __device__ __forceinline__ void static_for(F &&f)
 // 13.2 .. 15.3 us with; kernel 21.9 -> 19.2 us together with the SIMD-true role placement below.
 // r05: the head start of a generation (quarter chunks) arrives with the launch — `balance` = 1 | bias(gen 0) << 8 | bias(gen 1) << 12 | bias(gen 2) << 16 |
 // bias(gen 3) << 20, default 9, 6, 3, 0 = r04's 3 (3 - gen) — so that it can be tuned per handle (MPPI_TUNE_PC_BALANCE) without a rebuild.
+// The level: min(3, boost + 3 - min(3, floor(v / 4n))) with v = 16 i + 4 bias >= 0. The quotient is only needed up to 3, so three scalar
+// compares give it — a division by the runtime n was expanded (v_cvt, v_rcp_iflag_f32, v_mul, v_cvt, v_readfirstlane and ~30 scalar
+// instructions) in every slot of the producers' unrolled horizon loop and in every chunk of the consumer's.
+__host__ __device__ constexpr int pc_prio_level(int i, int n, int bias, int boost)
+{
+    const int v = 16 * i + 4 * bias, n4 = 4 * n;
+    const int lvl = boost + 3 - ((v >= n4 ? 1 : 0) + (v >= 2 * n4 ? 1 : 0) + (v >= 3 * n4 ? 1 : 0));
+    return lvl < 3 ? lvl : 3;
+}
+// (the formula the compares replace; -DMPPI_PC_PRIO_DIV builds it back in for A/B timing, tools/ablate.py)
+__host__ __device__ constexpr int pc_prio_level_div(int i, int n, int bias, int boost)
+{
+    const int q = (16 * i + 4 * bias) / (4 * n);
+    const int lvl = boost + 3 - (q < 3 ? q : 3);
+    return lvl < 3 ? lvl : 3;
+}
+// every chunk count the kernels are instantiated for (NSLOT <= 11), every chunk index, head start and boost
+constexpr bool pc_prio_levels_agree()
+{
+    for (int n = 1; n <= 11; ++n)
+        for (int i = 0; i <= n; ++i)
+            for (int bias = 0; bias < 16; ++bias)
+                for (int boost = 0; boost <= 3; ++boost)
+                    if (pc_prio_level(i, n, bias, boost) != pc_prio_level_div(i, n, bias, boost)) return false;
+    return true;
+}
+static_assert(pc_prio_levels_agree(), "pc_prio_level: the compares must give the division's level");
+
 __device__ __forceinline__ void pc_set_prio(int i, int n, int gen, int balance, int boost = 0)
 {
     const int bias = (balance >> (8 + 4 * min(gen, 3))) & 15; // quarter chunks
-    const int lvl = min(3, boost + 3 - min(3, (16 * i + 4 * bias) / (4 * n)));
+#if defined(MPPI_PC_PRIO_DIV)
+    const int lvl = pc_prio_level_div(i, n, bias, boost);
+#else
+    const int lvl = pc_prio_level(i, n, bias, boost);
+#endif
     switch (lvl) {
     case 0: __builtin_amdgcn_s_setprio(0); break;
     case 1: __builtin_amdgcn_s_setprio(1); break;

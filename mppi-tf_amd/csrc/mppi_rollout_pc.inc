@@ -84,6 +84,8 @@
         const unsigned int gk = (unsigned int)C->k_offset + (unsigned int)(k0 + lane); // the global sample index: below 2^31 + 64
         const unsigned long long base = step_ctr[0] * (unsigned long long)NG;
         const unsigned long long seed = C->seed;
+        // what the Philox rounds of every group of this lane share, once (blocks base * A .. (base + NG) * A - 1)
+        const PhiloxLane plane = make_philox_lane(seed, gk, base * A, (base + (unsigned long long)NG) * A - 1);
         float eps_r[NREG];
         PcProducerConsts<A> pcst; // SGPR-resident copy: no constant re-fetch after the barriers
         pcst.template load<DIAG>(C);
@@ -96,7 +98,7 @@
             if (balance) pc_set_prio(i, nch, gen, balance);
             if (PASS == PC_PASS_WEIGHTS && i < nch && g < NG) { // the noise alone: nothing is published, no chunk barrier
                 float z[4 * A];
-                MPPI_NORMALS_GROUP_UB(A, seed, gk, base + (unsigned long long)g, z);
+                MPPI_NORMALS_GROUP_UB(A, seed, gk, plane, base + (unsigned long long)g, z);
 #pragma unroll
                 for (int tl = 0; tl < 4; ++tl) {
                     float zz[A], e[A];
@@ -120,7 +122,7 @@
                         for (int j = 0; j < A; ++j) ug[tl][j] = U_dev[tt * A + j];
                     }
                     float z[4 * A];
-                    MPPI_NORMALS_GROUP_UB(A, seed, gk, base + (unsigned long long)g, z);
+                    MPPI_NORMALS_GROUP_UB(A, seed, gk, plane, base + (unsigned long long)g, z);
 #pragma unroll
                     for (int tl = 0; tl < 4; ++tl) {
                         const int t = 4 * g + tl;

@@ -331,6 +331,7 @@ __global__ __launch_bounds__(64 * (NP + 1), ((MODE & STEP_FUSE) ? 2 : NP == 5 ? 
         const unsigned int gk = (unsigned int)C->k_offset + (unsigned int)(k0 + lane);
         const unsigned long long base = (PRE ? sa.step_index : step_ctr[0]) * (unsigned long long)NG; // (PRE: step n-1's finish has not run yet — the host's mirror)
         const unsigned long long seed = C->seed;
+        const PhiloxLane plane = make_philox_lane(seed, gk, base * A, (base + (unsigned long long)NG) * A - 1); // as k_rollout_pc
         float eps_r[NREG];
         PcProducerConsts<A> pcst;
         pcst.template load<DIAG>(C);
@@ -342,7 +343,7 @@ __global__ __launch_bounds__(64 * (NP + 1), ((MODE & STEP_FUSE) ? 2 : NP == 5 ? 
             const int g = NP * i + p;
             if (i < nch && g < NG) {
                 float z[4 * A];
-                MPPI_NORMALS_GROUP_UB(A, seed, gk, base + (unsigned long long)g, z);
+                MPPI_NORMALS_GROUP_UB(A, seed, gk, plane, base + (unsigned long long)g, z);
 #pragma unroll
                 for (int tl = 0; tl < 4; ++tl) {
                     float zz[A], e[A];

@@ -24,6 +24,8 @@ VARIANTS = {
     "pc_neither": ["MPPI_PC_ABL=3"],
     "kind_per_step": ["MPPI_PC_KIND_PER_STEP"],  # k_rollout_pc: the action-cost form tested in every step (r04) instead of once around the producers' loop (r05; tools/ab_kind.py)
     "consumer_boost": ["MPPI_PC_CONSUMER_BOOST=1"],  # k_rollout_pc: the consumer wave one priority level above its progress level
+    "prio_div": ["MPPI_PC_PRIO_DIV"],  # k_rollout_pc: the priority level by a runtime division again instead of three compares
+    "no_lane_consts": ["MPPI_PHILOX_NO_LANE_CONSTS"],  # the producers' Philox without the per-lane constants (PhiloxLane): every group computes everything
     "finish_s0": ["MPPI_FINISH_STAGE=0"],
     "finish_s1": ["MPPI_FINISH_STAGE=1"],
     "finish_s2": ["MPPI_FINISH_STAGE=2"],

@@ -605,11 +605,11 @@ static hipError_t per_a(mppi_handle *h, hipError_t (*mppi_unit_a::*fn)(P...), Ar
     return u ? (u->*fn)(h, args...) : hipErrorInvalidValue;
 }
 
-static hipError_t launch_tile(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev,
+static hipError_t launch_tile(mppi_handle *h, const DevConsts *consts, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev,
                               const float *eps, float *cost, float *part, float *noise_out)
 {
     if (!h->no_rollout.empty()) return hipErrorNotSupported;
-    return per_a(h, &mppi_unit_a::tile, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
+    return per_a(h, &mppi_unit_a::tile, consts, st, src, mode, x_dev, U_dev, eps, cost, part, noise_out);
 }
 
 // the point-mass model with the quadratic (diagonal or dense Q) or the elliptic state cost; horizon groups per producer must fit the registers
@@ -645,40 +645,95 @@ static Route rollout_route(const mppi_handle *h, int src, const float *noise_out
     return philox && pc_eligible(h) ? ROUTE_PC : ROUTE_TILE;
 }
 
-// the next rollout launch on this profiled step's rollout events (hipExtLaunchKernel: the dispatch's own begin / end), or on none
-static void kernel_events(mppi_handle *h, bool on) { h->kev0 = on ? h->ev[4 * h->prof_n + 0] : nullptr; h->kev1 = on ? h->ev[4 * h->prof_n + 1] : nullptr; }
+// ---- the profiling slot: the one place that knows where a profiled step's events are. The slot index stays on the handle (a sharded step
+// spans two C calls: mppi_shard_partial* writes the rollout events of slot prof_n, mppi_shard_finish commits it); the events of the
+// launch at hand are handed to it as an argument (mppi_kev).
+struct ProfSlot { // the events of the step being enqueued, or none: it is not profiled
+    mppi_kev rollout, finish;
+    explicit operator bool() const { return rollout.begin != nullptr; }
+};
+static ProfSlot prof_slot(mppi_handle *h)
+{
+    if (h->prof_n >= h->prof_cap) return {};
+    hipEvent_t *ev = &h->ev[4 * h->prof_n];
+    return {{ev[0], ev[1]}, {ev[2], ev[3]}};
+}
+static void prof_commit(mppi_handle *h, hipStream_t st) { h->prof_stream = st; h->prof_n++; }
+// a profiled step that is one launch has no finish launch: an empty finish interval, and the step is recorded
+static hipError_t prof_one_launch(mppi_handle *h, ProfSlot p, hipStream_t st)
+{
+    if (!p) return hipSuccess;
+    if (hipError_t e = hipEventRecord(p.finish.begin, st); e != hipSuccess) return e;
+    if (hipError_t e = hipEventRecord(p.finish.end, st); e != hipSuccess) return e;
+    prof_commit(h, st);
+    return hipSuccess;
+}
 
-// Combine nb records (element (b,col) at recs[b*sb + col*sc]) and, if apply, update: U' = U_in + V/eta -> U_out,
-// u_out = U'[0]. More than 1024 records are first folded 16:1 (k_combine_group) into row-major scratch.
-static hipError_t launch_finish(mppi_handle *h, hipStream_t st, const float *recs, int sb, int sc, int nb,
-                                const float *U_in, float *U_out, float *u_out, float *record_out, int apply, bool xchg = false, unsigned armed_seq = 0,
-                                const FinishPre pre = FinishPre{nullptr, nullptr, 0u, 0ull})
+// One rollout launch on `route`, through the 13-state, learned-model, producer/consumer or tile launcher, on the handle's own sequence,
+// records and constants. kev: the profiled step's rollout events or none — the dispatch's own begin / end, except that the tile kernel
+// takes none and gets them recorded around its launch (`around`: so does any route). pass, range_given: k_rollout_pc's (MPPI_PC_PARAMS).
+static hipError_t launch_rollout(mppi_handle *h, hipStream_t st, Route route, mppi_kev kev, int src, int mode, const float *x_dev, const float *eps,
+                                 float *cost, float *noise_out, int pass = PC_PASS_PLAIN, bool range_given = false, bool around = false)
+{
+    const bool record = kev.begin && (around || route == ROUTE_TILE);
+    const mppi_kev own = record ? mppi_kev{} : kev;
+    hipError_t e = record ? hipEventRecord(kev.begin, st) : hipSuccess;
+    if (e != hipSuccess) return e;
+    switch (route) {
+    case ROUTE_GEN: e = mppi_launch_gen(h, h->dC, st, own, src, mode, x_dev, h->U_cur(), eps, cost, h->d_part, noise_out); break;
+    case ROUTE_MLP: e = per_a(h, &mppi_unit_a::mlp, st, own, src, mode, x_dev, (const float *)h->U_cur(), eps, cost); break;
+    case ROUTE_PC: e = per_a(h, &mppi_unit_a::pc, st, own, x_dev, pass, range_given); break;
+    case ROUTE_TILE: e = launch_tile(h, h->dC, st, src, mode, x_dev, h->U_cur(), eps, cost, h->d_part, noise_out); break;
+    default: e = hipErrorInvalidValue;
+    }
+    // records were made: from the raw costs at the range's temperature (the weights-only pass of normalizeCost), else at lambda
+    if (mode == MODE_ROLLOUT || mode == MODE_COSTS_GIVEN) h->norm_two_pass = route == ROUTE_PC && pass == PC_PASS_WEIGHTS;
+    if (e == hipSuccess && record) e = hipEventRecord(kev.end, st);
+    return e;
+}
+
+// What launch_finish combines and writes: n records (element (b, col) at recs[b*sb + col*sc]) and, if apply, the update:
+// U' = U_in + V/eta -> U_out, u_out = U'[0].
+struct Finish {
+    const float *recs = nullptr;
+    int sb = 1, sc = 0, n = 0;
+    const float *nil_dev = nullptr; // the temperature the records were made at where it is not lambda (d_mm + 2: the weights-only pass of normalizeCost); whoever made the records fills it in
+    const float *U_in = nullptr;
+    float *U_out = nullptr, *u_out = nullptr, *record_out = nullptr;
+    int apply = 1;
+    bool xchg = false;      // the finish that exchanges the records with the peers' inboxes first (mppi_shard_p2p_step)
+    unsigned armed_seq = 0; // of an armed launch: the finish obeys tile 0's verdict on it
+    FinishPre pre = FinishPre{nullptr, nullptr, 0u, 0ull};
+};
+// the common case: the handle's own d_part (every slot: those no tile owns hold neutral records) onto its own sequence
+static Finish own_records(const mppi_handle *h) { return Finish{h->d_part, 1, h->nbp, h->nbp, nullptr, h->U_cur(), h->U_other()}; }
+
+// More than 1024 records are first folded 16:1 (k_combine_group) into row-major scratch.
+static hipError_t launch_finish(mppi_handle *h, hipStream_t st, Finish f)
 {
     // a profiled step = the rollout kernel + the finish that applies the update
-    TraceRange tr(h, apply ? "mppi:finish" : "mppi:record");
-    const bool prof = apply && h->prof_n < h->prof_cap;
-    const float *nil_dev = h->norm_two_pass ? h->d_mm + 2 : nullptr; // this step's records were made at the temperature k_cost_minmax left there
+    TraceRange tr(h, f.apply ? "mppi:finish" : "mppi:record");
+    const ProfSlot p = f.apply ? prof_slot(h) : ProfSlot{};
     float *out = h->d_part2;
-    while (nb > 1024) {
-        const int ng = (nb + kGroup - 1) / kGroup;
-        hipLaunchKernelGGL(k_combine_group, dim3(ng), dim3(kThreads), 0, st, recs, sb, sc, nb, h->HA, h->hc.neg_inv_lambda, out, nil_dev);
+    while (f.n > 1024) {
+        const int ng = (f.n + kGroup - 1) / kGroup;
+        hipLaunchKernelGGL(k_combine_group, dim3(ng), dim3(kThreads), 0, st, f.recs, f.sb, f.sc, f.n, h->HA, h->hc.neg_inv_lambda, out, f.nil_dev);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        recs = out; sb = 2 + h->HA; sc = 1; nb = ng;
+        f.recs = out; f.sb = 2 + h->HA; f.sc = 1; f.n = ng;
         out = h->d_part3;
     }
-    // profiled: the finish kernel's own dispatch begin/end (hipExtLaunchKernel events), like the rollout kernel's
-    hipEvent_t f0 = prof ? h->ev[4 * h->prof_n + 2] : nullptr, f1 = prof ? h->ev[4 * h->prof_n + 3] : nullptr;
-    if (xchg)
-        hipExtLaunchKernelGGL(k_finish_cols_xchg, dim3(h->HA), dim3(kThreads), 0, st, f0, f1, 0, recs, sb, sc, nb, h->HA, h->a, h->hc.neg_inv_lambda,
-                              U_in, U_out, u_out, h->d_step, h->d_dbg, h->xchg_peers, h->shard_count, h->shard_rank, ++h->xchg_seq,
+    const mppi_kev kev = p.finish; // profiled: the finish kernel's own dispatch begin/end (hipExtLaunchKernel events), like the rollout kernel's
+    if (f.xchg)
+        hipExtLaunchKernelGGL(k_finish_cols_xchg, dim3(h->HA), dim3(kThreads), 0, st, kev.begin, kev.end, 0, f.recs, f.sb, f.sc, f.n, h->HA, h->a,
+                              h->hc.neg_inv_lambda, f.U_in, f.U_out, f.u_out, h->d_step, h->d_dbg, h->xchg_peers, h->shard_count, h->shard_rank, ++h->xchg_seq,
                               h->xchg_timeout_ticks, h->d_xchg_status, h->d_xchg_dead, (const float *)h->d_clip);
     else
-        hipExtLaunchKernelGGL(k_finish_cols, dim3(h->HA), dim3(kThreads), 0, st, f0, f1, 0, recs, sb, sc, nb, h->HA, h->a, h->hc.neg_inv_lambda,
-                              U_in, U_out, u_out, record_out, apply, h->d_step, h->d_dbg, (const float *)h->d_clip, nil_dev,
-                              armed_seq ? (const unsigned long long *)h->d_decision : (const unsigned long long *)nullptr, armed_seq, pre);
+        hipExtLaunchKernelGGL(k_finish_cols, dim3(h->HA), dim3(kThreads), 0, st, kev.begin, kev.end, 0, f.recs, f.sb, f.sc, f.n, h->HA, h->a,
+                              h->hc.neg_inv_lambda, f.U_in, f.U_out, f.u_out, f.record_out, f.apply, h->d_step, h->d_dbg, (const float *)h->d_clip, f.nil_dev,
+                              f.armed_seq ? (const unsigned long long *)h->d_decision : (const unsigned long long *)nullptr, f.armed_seq, f.pre);
     hipError_t e = hipGetLastError();
-    if (prof && e == hipSuccess) { h->prof_stream = st; h->prof_n++; }
+    if (p && e == hipSuccess) prof_commit(h, st);
     return e;
 }
 
@@ -802,75 +857,76 @@ static hipError_t ensure_record_layout(mppi_handle *h, hipStream_t st, int n_til
     return hipGetLastError();
 }
 
-// rollouts of this shard -> partial records in d_part; *nrec = how many. Handles normalizeCost.
-static mppi_status enqueue_partials(mppi_handle *h, hipStream_t st, int src, const float *x_dev, const float *eps, float *noise_out, int *nrec)
+// ---- Py normalizeCost (controller_base.py:468-474): costs, global min/max, then the update on c' = (c-min)/(max-min) with the SAME noise
+// (regenerated from the same Philox counters). Two halves, which an unsharded step (enqueue_partials) runs back to back and a K-sharded
+// one as two calls with the ranks' agreement on the range between them (mppi_shard_cost_range, mppi_shard_partial_normalized).
+// Fast form on the producer/consumer kernel (ROUTE_PC): exp(-(c' - min c')/lambda) = exp(-(c - min c)/(lambda (max - min))), so the normalised
+// update is the plain one at another temperature. A pass at lambda for the costs; then the weights-only pass (PC_PASS_WEIGHTS, r04): no
+// rollouts — the weights from the stored costs, the noise regenerated for the weighted sums; records at the range's temperature, which the
+// finish reads from d_mm[2] (r03: a full second rollout pass, 42 us at C3; the tile kernel's two passes 76). Else: cost pass,
+// k_cost_normalize, record pass from the normalised costs at lambda.
+// (ADVICE r03) pc_eligible's horizon bound depends on pc_np, and pc_np on THIS shard's tile count (or a per-handle tuning): with
+// 132 < H <= 160 and ragged shards straddling 512 tiles one rank would make raw-cost records at the range temperature and another
+// normalised-cost records at lambda. A sharded handle therefore takes the fast form only below the bound that holds for every pc_np: the
+// form depends on the configuration only, never on the shard's size, and all ranks make their records in the same units.
+static bool norm_fast(const mppi_handle *h) { return h->hc.model_kind != MPPI_MODEL_MLP && !h->is_gen && pc_eligible(h) && (h->shard_count == 1 || h->H <= 132); }
+static Route norm_route(const mppi_handle *h, int src, const float *noise_out)
+{
+    const Route r = rollout_route(h, src, noise_out, false);
+    return r == ROUTE_PC && !norm_fast(h) ? ROUTE_TILE : r;
+}
+
+// First half: the costs into d_cost. range_out (the sharded calls): this shard's {-min, max} goes there as well. Fast form: unsharded, the
+// PC_PASS_COSTS pass, every tile leaving its (min, max) in d_tile_mm; with range_out the plain pass (its records, at lambda, are overwritten
+// by the second half) and k_cost_minmax. Else the cost-only pass, which a profiled step brackets (kev: the dominant launch), and k_cost_minmax.
+static mppi_status norm_costs(mppi_handle *h, hipStream_t st, Route route, mppi_kev kev, int src, const float *x_dev, const float *eps, float *noise_out, float *range_out)
+{
+    if (route == ROUTE_PC) HIP_TRY(h, launch_rollout(h, st, route, mppi_kev{}, src, MODE_ROLLOUT, x_dev, eps, h->d_cost, noise_out, range_out ? PC_PASS_PLAIN : PC_PASS_COSTS));
+    else HIP_TRY(h, launch_rollout(h, st, route, kev, src, MODE_COST_ONLY, x_dev, eps, h->d_cost, noise_out, PC_PASS_PLAIN, false, true));
+    if (route == ROUTE_PC && !range_out) return MPPI_OK;
+    hipLaunchKernelGGL(k_cost_minmax, dim3(1), dim3(1024), 0, st, h->d_cost, h->K_local, h->d_mm, 0.0f, (float *)nullptr, range_out);
+    HIP_TRY(h, hipGetLastError());
+    return MPPI_OK;
+}
+
+// Second half: the records from the costs of the first, and where the finish finds their temperature (made->nil_dev). Fast form: the
+// weights-only pass (kev: a profiled step reports this pass, the one whose records are used); range_given: the range is in d_mm already.
+// Else from the costs normalised with the range in d_mm; a learned point-mass model's records come from the tile kernel.
+static mppi_status norm_records(mppi_handle *h, hipStream_t st, Route route, mppi_kev kev, int src, const float *x_dev, const float *eps, bool range_given, Finish *made)
+{
+    if (route == ROUTE_PC) {
+        HIP_TRY(h, launch_rollout(h, st, route, kev, src, MODE_ROLLOUT, x_dev, eps, h->d_cost, nullptr, PC_PASS_WEIGHTS, range_given));
+        made->nil_dev = h->d_mm + 2; // the temperature k_rollout_pc / k_cost_minmax / k_range_apply left there
+        return MPPI_OK;
+    }
+    hipLaunchKernelGGL(k_cost_normalize, dim3((h->K_local + 255) / 256), dim3(256), 0, st, h->d_cost, h->K_local, h->d_mm, h->d_cost2);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, launch_rollout(h, st, route == ROUTE_GEN ? ROUTE_GEN : ROUTE_TILE, mppi_kev{}, src, MODE_COSTS_GIVEN, x_dev, eps, h->d_cost2, nullptr));
+    return MPPI_OK;
+}
+
+// rollouts of this shard -> partial records in d_part; *made = where they are, how many, their temperature. Handles normalizeCost.
+static mppi_status enqueue_partials(mppi_handle *h, hipStream_t st, int src, const float *x_dev, const float *eps, float *noise_out, Finish *made)
 {
     const Route route = rollout_route(h, src, noise_out, false);
-    const bool mlp = route == ROUTE_MLP;
-    const bool gen = route == ROUTE_GEN;
     TraceRange tr(h, "mppi:rollout");
-    *nrec = h->nbp; // every slot: those no tile owns hold neutral records
-    h->norm_two_pass = 0;
-    HIP_TRY(h, ensure_record_layout(h, st, (mlp && !h->normalize) ? h->nb_mlp : h->nb)); // (normalizeCost: the tile kernel writes the records)
+    *made = own_records(h);
+    HIP_TRY(h, ensure_record_layout(h, st, (route == ROUTE_MLP && !h->normalize) ? h->nb_mlp : h->nb)); // (normalizeCost: the tile kernel writes the records)
+    const mppi_kev kev = prof_slot(h).rollout;
     if (!h->normalize) {
-        const bool prof = h->prof_n < h->prof_cap;
-        const bool kernel_events_on = prof && route != ROUTE_TILE; // the kernel's own begin/end; the tile kernel: events around the launch
-        if (prof && !kernel_events_on) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 0], st));
-        kernel_events(h, kernel_events_on);
-        hipError_t le = gen ? mppi_launch_gen(h, st, src, MODE_ROLLOUT, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out)
-                      : mlp ? per_a(h, &mppi_unit_a::mlp, st, src, MODE_ROLLOUT, x_dev, h->U_cur(), eps, h->d_cost)
-                      : route == ROUTE_PC ? per_a(h, &mppi_unit_a::pc, st, x_dev)
-                                          : launch_tile(h, st, src, MODE_ROLLOUT, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out);
-        h->kev0 = h->kev1 = nullptr;
-        HIP_TRY(h, le);
-        if (prof && !kernel_events_on) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 1], st));
+        HIP_TRY(h, launch_rollout(h, st, route, kev, src, MODE_ROLLOUT, x_dev, eps, h->d_cost, noise_out));
         return MPPI_OK;
     }
     if (h->shard_count != 1) return fail(h, MPPI_ERR_UNSUPPORTED, "normalize_cost on a sharded handle: mppi_shard_cost_range, reduce the ranges over the ranks, mppi_shard_partial_normalized");
-    // Py normalizeCost (controller_base.py:468-474): costs, global min/max, then the update on
-    // c' = (c-min)/(max-min) with the SAME noise (regenerated from the same Philox counters).
-    if (route == ROUTE_PC) {
-        // Fast form on the producer/consumer kernel: exp(-(c' - min c')/lambda) = exp(-(c - min c)/(lambda (max - min))), so the
-        // normalised update is the plain one at another temperature. Pass 1 (PC_PASS_COSTS): the plain pass at lambda for the costs, every tile
-        // leaving its (min, max); pass 2 (PC_PASS_WEIGHTS, r04): no rollouts — the global range from the tile pairs, the weights from the stored
-        // costs, the noise regenerated (same Philox counters) for the weighted sums; records at the range's temperature, which the finish reads
-        // from d_mm[2]. r03: a full second rollout pass with k_cost_minmax between the two (42 us at C3; the tile kernel's two passes 76).
-        const bool prof2 = h->prof_n < h->prof_cap;
-        h->kev0 = h->kev1 = nullptr;
-        h->pc_pass = PC_PASS_COSTS;
-        hipError_t le = per_a(h, &mppi_unit_a::pc, st, x_dev);
-        h->pc_pass = PC_PASS_PLAIN;
-        HIP_TRY(h, le);
-        kernel_events(h, prof2); // a profiled step reports the second pass (the one whose records are used)
-        // every workgroup of the second pass reduces the nb tile pairs itself: nb^2 x 8 bytes of L2 reads in all — 8 MB at 1024 tiles, too much
-        // beyond a few thousand (K > 131072 on one GPU): there the range comes from ONE k_cost_minmax launch over the costs instead
-        const int many_tiles = h->nb > 2048;
-        if (many_tiles) {
-            hipLaunchKernelGGL(k_cost_minmax, dim3(1), dim3(1024), 0, st, h->d_cost, h->K_local, h->d_mm, h->hc.neg_inv_lambda, h->d_mm + 3, (float *)nullptr);
-            HIP_TRY(h, hipGetLastError());
-        }
-        h->pc_pass = PC_PASS_WEIGHTS; h->pc_range_given = many_tiles;
-        le = per_a(h, &mppi_unit_a::pc, st, x_dev);
-        h->pc_pass = PC_PASS_PLAIN; h->pc_range_given = 0;
-        h->kev0 = h->kev1 = nullptr;
-        HIP_TRY(h, le);
-        h->norm_two_pass = 1;
-        return MPPI_OK;
+    if (mppi_status s = norm_costs(h, st, route, kev, src, x_dev, eps, noise_out, nullptr); s != MPPI_OK) return s;
+    // every workgroup of the weights-only pass reduces the nb tile pairs itself: nb^2 x 8 bytes of L2 reads in all — 8 MB at 1024 tiles, too much
+    // beyond a few thousand (K > 131072 on one GPU): there the range comes from ONE k_cost_minmax launch over the costs instead
+    const bool many_tiles = route == ROUTE_PC && h->nb > 2048;
+    if (many_tiles) {
+        hipLaunchKernelGGL(k_cost_minmax, dim3(1), dim3(1024), 0, st, h->d_cost, h->K_local, h->d_mm, h->hc.neg_inv_lambda, h->d_mm + 3, (float *)nullptr);
+        HIP_TRY(h, hipGetLastError());
     }
-    const bool prof_n = h->prof_n < h->prof_cap; // a profiled step brackets the cost pass (the dominant launch) here
-    if (prof_n) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 0], st));
-    if (gen) HIP_TRY(h, mppi_launch_gen(h, st, src, MODE_COST_ONLY, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out));
-    else if (mlp) HIP_TRY(h, per_a(h, &mppi_unit_a::mlp, st, src, MODE_COST_ONLY, x_dev, h->U_cur(), eps, h->d_cost));
-    else HIP_TRY(h, launch_tile(h, st, src, MODE_COST_ONLY, x_dev, h->U_cur(), eps, h->d_cost, h->d_part, noise_out));
-    if (prof_n) HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 1], st));
-    hipLaunchKernelGGL(k_cost_minmax, dim3(1), dim3(1024), 0, st, h->d_cost, h->K_local, h->d_mm, 0.0f, (float *)nullptr, (float *)nullptr);
-    HIP_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL(k_cost_normalize, dim3((h->K_local + 255) / 256), dim3(256), 0, st, h->d_cost, h->K_local, h->d_mm, h->d_cost2);
-    HIP_TRY(h, hipGetLastError());
-    if (gen) HIP_TRY(h, mppi_launch_gen(h, st, src, MODE_COSTS_GIVEN, x_dev, h->U_cur(), eps, h->d_cost2, h->d_part, nullptr));
-    else HIP_TRY(h, launch_tile(h, st, src, MODE_COSTS_GIVEN, x_dev, h->U_cur(), eps, h->d_cost2, h->d_part, nullptr));
-    *nrec = h->nbp;
-    return MPPI_OK;
+    return norm_records(h, st, route, kev, src, x_dev, eps, many_tiles, made);
 }
 
 static mppi_status ensure_eps(mppi_handle *h)
@@ -995,20 +1051,31 @@ extern "C" mppi_status mppi_set_mlp(mppi_handle *h, const mppi_mlp_desc *d)
 static mppi_status fused_step(mppi_handle *h, hipStream_t st, const float *x_dev, float *u_dev)
 {
     TraceRange tr(h, "mppi:rollout");
-    const bool prof = h->prof_n < h->prof_cap;
-    kernel_events(h, prof); // the launch's own begin / end
+    const ProfSlot p = prof_slot(h);
     const mppi_step_launch L{STEP_FUSE, x_dev, h->U_cur(), h->U_other(), u_dev, h->next_seq()};
-    const hipError_t e = per_a(h, &mppi_unit_a::step, st, &L);
-    h->kev0 = h->kev1 = nullptr;
-    HIP_TRY(h, e);
-    if (prof) { // (no finish launch: an empty interval)
-        HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 2], st));
-        HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 3], st));
-        h->prof_stream = st;
-        h->prof_n++;
-    }
+    HIP_TRY(h, per_a(h, &mppi_unit_a::step, st, p.rollout, &L)); // the launch's own begin / end
+    HIP_TRY(h, prof_one_launch(h, p, st));
     HIP_TRY(h, advance_sequence(h, st));
     return MPPI_OK;
+}
+
+// The plain control step in two halves, which a K-sharded step runs as two calls with the record exchange between them (mppi_shard_partial,
+// mppi_shard_finish): enqueue_partials makes the records; this finishes them with the update and advances the sequence.
+static mppi_status finish_step(mppi_handle *h, hipStream_t st, const Finish &f)
+{
+    HIP_TRY(h, launch_finish(h, st, f));
+    HIP_TRY(h, advance_sequence(h, st));
+    return MPPI_OK;
+}
+// ... and both in one, on Philox noise or the noise in eps (src), xchg: with the in-kernel record exchange. ONE launch where the fused
+// route serves: never with the exchange, never with injected noise (rollout_route).
+static mppi_status plain_step(mppi_handle *h, hipStream_t st, int src, const float *x_dev, const float *eps, float *u_dev, bool xchg = false)
+{
+    if (!xchg && rollout_route(h, src, nullptr, true) == ROUTE_STEP) return fused_step(h, st, x_dev, u_dev);
+    Finish f;
+    if (mppi_status s = enqueue_partials(h, st, src, x_dev, eps, nullptr, &f); s != MPPI_OK) return s;
+    f.u_out = u_dev; f.xchg = xchg;
+    return finish_step(h, st, f);
 }
 
 // Arm a step: the launch(es) that run it as soon as mppi_next has stored x. U_in / U_out: the sequence as it stands once every step
@@ -1019,11 +1086,11 @@ static mppi_status arm_launch(mppi_handle *h, const float *U_in, float *U_out, u
     float *u_arg = h->d_pin + 2 * kMaxS;
     if (!(mode & STEP_FUSE)) HIP_TRY(h, ensure_record_layout(h, h->stream, h->nb));
     const mppi_step_launch L{mode, nullptr, U_in, U_out, u_arg, seq};
-    h->kev0 = h->kev1 = nullptr;
-    HIP_TRY(h, per_a(h, &mppi_unit_a::step, h->stream, &L));
+    HIP_TRY(h, per_a(h, &mppi_unit_a::step, h->stream, mppi_kev{}, &L));
     if (!(mode & STEP_FUSE)) {
-        h->norm_two_pass = 0;
-        HIP_TRY(h, launch_finish(h, h->stream, h->d_part, 1, h->nbp, h->nbp, U_in, U_out, u_arg, nullptr, 1, false, seq));
+        Finish f = own_records(h);
+        f.U_in = U_in; f.U_out = U_out; f.u_out = u_arg; f.armed_seq = seq;
+        HIP_TRY(h, launch_finish(h, h->stream, f));
     }
     return MPPI_OK;
 }
@@ -1083,27 +1150,19 @@ static mppi_status pre_step(mppi_handle *h, const float *x_dev, float *u_dev)
     const unsigned long long *ugr_in = h->d_ugr + (size_t)h->pre_buf * h->HA;
     unsigned long long *ugr_out = h->d_ugr + (size_t)(1 - h->pre_buf) * h->HA;
     const bool fused = fuse_ok(h); // <= 128 tiles: the column waves of the same grid finish the step (and write the next step's granules)
+    const ProfSlot p = prof_slot(h);
     {
         TraceRange tr(h, "mppi:rollout");
-        const bool prof = h->prof_n < h->prof_cap;
-        kernel_events(h, prof);
         mppi_step_launch L{STEP_PRE | (fused ? STEP_FUSE : 0), x_dev, h->U_cur(), h->U_other(), u_dev, seq};
         L.ugr = ugr_in; L.utag = h->pre_tag; L.step_index = h->pre_step; L.ugr_out = fused ? ugr_out : nullptr;
-        const hipError_t e = per_a(h, &mppi_unit_a::step, st, &L);
-        h->kev0 = h->kev1 = nullptr;
-        HIP_TRY(h, e);
+        HIP_TRY(h, per_a(h, &mppi_unit_a::step, st, p.rollout, &L));
     }
     if (h->pre_count == 0) HIP_TRY(h, hipEventRecord(h->pre_ev, st)); // (start-up: see above)
-    h->norm_two_pass = 0;
     if (!fused) {
-        HIP_TRY(h, launch_finish(h, st, h->d_part, 1, h->nbp, h->nbp, h->U_cur(), h->U_other(), u_dev, nullptr, 1, false, 0,
-                                 FinishPre{ugr_in, ugr_out, seq, h->pre_step}));
-    } else if (h->prof_n < h->prof_cap) { // (a profiled fused step has no finish launch: an empty interval, as fused_step records it)
-        HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 2], st));
-        HIP_TRY(h, hipEventRecord(h->ev[4 * h->prof_n + 3], st));
-        h->prof_stream = st;
-        h->prof_n++;
-    }
+        Finish f = own_records(h);
+        f.u_out = u_dev; f.pre = FinishPre{ugr_in, ugr_out, seq, h->pre_step};
+        HIP_TRY(h, launch_finish(h, st, f));
+    } else HIP_TRY(h, prof_one_launch(h, p, st));
     if (h->pre_count == 0) HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->pre_ev, 0));
     if (h->pre_count == 1) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->pre_ev2, 0)); // rollout 3 behind the second stream's release
     h->U_advance(); // (no sequence filter on this path: step_shape_ok)
@@ -1120,13 +1179,7 @@ extern "C" mppi_status mppi_next_device(mppi_handle *h, const float *x_dev, floa
     MPPI_ENTER(h);
     TraceRange step_range(h, "mppi:step");
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    if (rollout_route(h, SRC_PHILOX, nullptr, true) == ROUTE_STEP) return fused_step(h, st, x_dev, u_dev);
-    int nrec = 0;
-    mppi_status s = enqueue_partials(h, st, SRC_PHILOX, x_dev, nullptr, nullptr, &nrec);
-    if (s != MPPI_OK) return s;
-    HIP_TRY(h, launch_finish(h, st, h->d_part, 1, nrec, nrec, h->U_cur(), h->U_other(), u_dev, nullptr, 1));
-    HIP_TRY(h, advance_sequence(h, st));
-    return MPPI_OK;
+    return plain_step(h, st, SRC_PHILOX, x_dev, nullptr, u_dev);
 }
 
 extern "C" mppi_status mppi_shard_partial(mppi_handle *h, const float *x_dev, float *record_dev, void *stream)
@@ -1135,27 +1188,17 @@ extern "C" mppi_status mppi_shard_partial(mppi_handle *h, const float *x_dev, fl
     if (!h || !x_dev || !record_dev) return h ? fail(h, MPPI_ERR_INVALID_ARG, "NULL device pointer") : MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h);
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    int nrec = 0;
-    mppi_status s = enqueue_partials(h, st, SRC_PHILOX, x_dev, nullptr, nullptr, &nrec);
-    if (s != MPPI_OK) return s;
-    HIP_TRY(h, launch_finish(h, st, h->d_part, 1, nrec, nrec, h->U_cur(), h->U_other(), h->d_u, record_dev, 0));
+    Finish f;
+    if (mppi_status s = enqueue_partials(h, st, SRC_PHILOX, x_dev, nullptr, nullptr, &f); s != MPPI_OK) return s;
+    f.u_out = h->d_u; f.record_out = record_dev; f.apply = 0;
+    HIP_TRY(h, launch_finish(h, st, f));
     return MPPI_OK;
 }
 
 // ---- normalizeCost on a K-sharded controller -----------------------------------------------------
 // c' = (c - min)/(max - min) needs the min and max over ALL samples (controller_base.py:468-474): each shard rolls its samples and
-// reports its own {-min, max}; the ranks reduce the pairs (ONE 2-float all-reduce(MAX)); each shard then
-// makes its record from costs normalised with the agreed range. Both halves take the path enqueue_partials takes on an unsharded
-// handle — two passes of k_rollout_pc where it serves the configuration, else cost pass + normalise + record pass; which of the two
-// depends on the configuration only, never on the shard's size: all ranks make their records in the same units.
-// (ADVICE r03) pc_eligible's horizon bound depends on pc_np, and pc_np on THIS shard's tile count (or a per-handle tuning): with
-// 132 < H <= 160 and ragged shards straddling 512 tiles one rank would make raw-cost records at the range temperature and another
-// normalised-cost records at lambda. A sharded handle therefore takes the fast form only below the bound that holds for every pc_np.
-static bool norm_fast(const mppi_handle *h)
-{
-    return h->hc.model_kind != MPPI_MODEL_MLP && !h->is_gen && pc_eligible(h) && (h->shard_count == 1 || h->H <= 132);
-}
-
+// reports its own {-min, max}; the ranks reduce the pairs (ONE 2-float all-reduce(MAX)); each shard then makes its record from costs
+// normalised with the agreed range. The two calls are the two halves of enqueue_partials' normalizeCost (norm_costs, norm_records).
 extern "C" mppi_status mppi_shard_cost_range(mppi_handle *h, const float *x_dev, float *range_dev, void *stream)
 {
     MPPI_NOT_BATCH(h, "mppi_shard_cost_range");
@@ -1163,17 +1206,8 @@ extern "C" mppi_status mppi_shard_cost_range(mppi_handle *h, const float *x_dev,
     if (!h->normalize) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_shard_cost_range: the handle was created without normalize_cost");
     MPPI_ENTER(h);
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    const bool mlp = h->hc.model_kind == MPPI_MODEL_MLP;
-    h->norm_two_pass = 0;
-    h->kev0 = h->kev1 = nullptr;
     HIP_TRY(h, ensure_record_layout(h, st, h->nb));
-    if (norm_fast(h)) HIP_TRY(h, per_a(h, &mppi_unit_a::pc, st, x_dev)); // its records (at lambda) are overwritten by the second pass
-    else if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, st, SRC_PHILOX, MODE_COST_ONLY, x_dev, h->U_cur(), nullptr, h->d_cost, h->d_part, nullptr));
-    else if (mlp) HIP_TRY(h, per_a(h, &mppi_unit_a::mlp, st, SRC_PHILOX, MODE_COST_ONLY, x_dev, h->U_cur(), nullptr, h->d_cost));
-    else HIP_TRY(h, launch_tile(h, st, SRC_PHILOX, MODE_COST_ONLY, x_dev, h->U_cur(), nullptr, h->d_cost, h->d_part, nullptr));
-    hipLaunchKernelGGL(k_cost_minmax, dim3(1), dim3(1024), 0, st, h->d_cost, h->K_local, h->d_mm, 0.0f, (float *)nullptr, range_dev);
-    HIP_TRY(h, hipGetLastError());
-    return MPPI_OK;
+    return norm_costs(h, st, norm_route(h, SRC_PHILOX, nullptr), prof_slot(h).rollout, SRC_PHILOX, x_dev, nullptr, nullptr, range_dev);
 }
 
 extern "C" mppi_status mppi_shard_partial_normalized(mppi_handle *h, const float *x_dev, const float *range_dev, float *record_dev, void *stream)
@@ -1183,25 +1217,13 @@ extern "C" mppi_status mppi_shard_partial_normalized(mppi_handle *h, const float
     if (!h->normalize) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_shard_partial_normalized: the handle was created without normalize_cost");
     MPPI_ENTER(h);
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    const bool fast = norm_fast(h);
-    h->kev0 = h->kev1 = nullptr;
     hipLaunchKernelGGL(k_range_apply, dim3(1), dim3(64), 0, st, range_dev, h->d_mm, h->hc.neg_inv_lambda, (float *)nullptr);
     HIP_TRY(h, hipGetLastError());
-    if (fast) { // the weights-only pass (PC_PASS_WEIGHTS) at the temperature of the agreed range (k_range_apply left it in d_mm[2]): the costs of
-                // mppi_shard_cost_range, the noise regenerated from the same Philox counters, records of the raw costs at that temperature
-        h->pc_pass = PC_PASS_WEIGHTS; h->pc_range_given = 1;
-        const hipError_t le = per_a(h, &mppi_unit_a::pc, st, x_dev);
-        h->pc_pass = PC_PASS_PLAIN; h->pc_range_given = 0;
-        HIP_TRY(h, le);
-        h->norm_two_pass = 1;
-    } else { // d_cost still holds this step's costs (mppi_shard_cost_range)
-        hipLaunchKernelGGL(k_cost_normalize, dim3((h->K_local + 255) / 256), dim3(256), 0, st, h->d_cost, h->K_local, h->d_mm, h->d_cost2);
-        HIP_TRY(h, hipGetLastError());
-        if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, st, SRC_PHILOX, MODE_COSTS_GIVEN, x_dev, h->U_cur(), nullptr, h->d_cost2, h->d_part, nullptr));
-        else HIP_TRY(h, launch_tile(h, st, SRC_PHILOX, MODE_COSTS_GIVEN, x_dev, h->U_cur(), nullptr, h->d_cost2, h->d_part, nullptr));
-        h->norm_two_pass = 0;
-    }
-    HIP_TRY(h, launch_finish(h, st, h->d_part, 1, h->nbp, h->nbp, h->U_cur(), h->U_other(), h->d_u, record_dev, 0));
+    // d_cost still holds this step's costs (mppi_shard_cost_range); the agreed range and its temperature are in d_mm now
+    Finish f = own_records(h);
+    if (mppi_status s = norm_records(h, st, norm_route(h, SRC_PHILOX, nullptr), prof_slot(h).rollout, SRC_PHILOX, x_dev, nullptr, true, &f); s != MPPI_OK) return s;
+    f.u_out = h->d_u; f.record_out = record_dev; f.apply = 0;
+    HIP_TRY(h, launch_finish(h, st, f));
     return MPPI_OK;
 }
 
@@ -1211,9 +1233,10 @@ extern "C" mppi_status mppi_shard_finish(mppi_handle *h, const float *records_de
     if (!h || !records_dev || !u_dev || n_records <= 0) return h ? fail(h, MPPI_ERR_INVALID_ARG, "bad records/u pointer or count") : MPPI_ERR_INVALID_ARG;
     MPPI_ENTER(h);
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    HIP_TRY(h, launch_finish(h, st, records_dev, 2 + h->HA, 1, n_records, h->U_cur(), h->U_other(), u_dev, nullptr, 1));
-    HIP_TRY(h, advance_sequence(h, st));
-    return MPPI_OK;
+    Finish f = own_records(h);
+    f.recs = records_dev; f.sb = 2 + h->HA; f.sc = 1; f.n = n_records; f.u_out = u_dev;
+    if (h->norm_two_pass) f.nil_dev = h->d_mm + 2; // the ranks' records are in the units of this handle's own (mppi_shard_partial_normalized)
+    return finish_step(h, st, f);
 }
 
 // One call per sharded step on the collective path (include/mppi_c.h): record -> the caller's all-gather (in place) -> finish.
@@ -1347,12 +1370,7 @@ extern "C" mppi_status mppi_shard_p2p_step(mppi_handle *h, const float *x_dev, f
     MPPI_ENTER(h);
     TraceRange step_range(h, "mppi:step");
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    int nrec = 0;
-    mppi_status s = enqueue_partials(h, st, SRC_PHILOX, x_dev, nullptr, nullptr, &nrec);
-    if (s != MPPI_OK) return s;
-    HIP_TRY(h, launch_finish(h, st, h->d_part, 1, nrec, nrec, h->U_cur(), h->U_other(), u_dev, nullptr, 1, true));
-    HIP_TRY(h, advance_sequence(h, st));
-    return MPPI_OK;
+    return plain_step(h, st, SRC_PHILOX, x_dev, nullptr, u_dev, true);
 }
 
 extern "C" mppi_status mppi_shard_p2p_status(mppi_handle *h, int *timed_out)
@@ -1464,16 +1482,7 @@ static mppi_status step_host(mppi_handle *h, const float *x, int n_x, const floa
     float *u_arg = h->d_pin + 2 * kMaxS;
     const bool spin_u = h->sync_spin && h->sg_window == 0; // with a sequence filter the step has one more kernel after u
     if (spin_u) for (int j = 0; j < h->a; ++j) uslot[j] = kUSentinel;
-    if (rollout_route(h, src, nullptr, true) == ROUTE_STEP) {
-        mppi_status s = fused_step(h, h->stream, x_arg, u_arg);
-        if (s != MPPI_OK) return s;
-    } else {
-        int nrec = 0;
-        mppi_status s = enqueue_partials(h, h->stream, src, x_arg, h->d_eps, nullptr, &nrec);
-        if (s != MPPI_OK) return s;
-        HIP_TRY(h, launch_finish(h, h->stream, h->d_part, 1, nrec, nrec, h->U_cur(), h->U_other(), u_arg, nullptr, 1));
-        HIP_TRY(h, advance_sequence(h, h->stream));
-    }
+    if (mppi_status s = plain_step(h, h->stream, src, x_arg, h->d_eps, u_arg); s != MPPI_OK) return s;
     // two calls within the soft deadline of each other: the host loop is fast enough for an armed launch to be fed in time
     if (may_arm && spin_u && (h->arm_always || gap_ns < (long long)h->arm_us * 1000ll)) {
         const unsigned seq = h->next_seq();
@@ -1715,14 +1724,6 @@ extern "C" mppi_status mppi_set_step_counter(mppi_handle *h, uint64_t step)
     return MPPI_OK;
 }
 
-// h->dC is member m's constants for the guard's scope: the lone kernels' launchers read the handle's constants there
-struct MemberConsts {
-    mppi_handle *h;
-    DevConsts *own;
-    MemberConsts(mppi_handle *h_, int m) : h(h_), own(h_->dC) { h->dC = own + m; }
-    ~MemberConsts() { h->dC = own; }
-};
-
 // one debug item of member `member` (a lone handle: 0)
 static mppi_status debug_get(mppi_handle *h, int member, int what, float *out, size_t n)
 {
@@ -1764,12 +1765,9 @@ static mppi_status debug_get(mppi_handle *h, int member, int what, float *out, s
         HIP_TRY(h, hipMemcpyAsync(h->d_step, &prev, sizeof(prev), hipMemcpyHostToDevice, h->stream));
         // noise-only pass of the tile kernel (the point mass) or of k_rollout_gen (the 13-state family), on the member's constants: reads
         // neither x nor any cost buffer and writes nothing but d_eps
-        hipError_t le;
-        {
-            MemberConsts own(h, member);
-            le = h->is_gen ? mppi_launch_gen(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps)
-                           : launch_tile(h, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
-        }
+        const DevConsts *own = h->dC + member;
+        const hipError_t le = h->is_gen ? mppi_launch_gen(h, own, h->stream, mppi_kev{}, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps)
+                                        : launch_tile(h, own, h->stream, SRC_PHILOX, MODE_NOISE_ONLY, h->d_x, h->U_cur(), nullptr, nullptr, nullptr, h->d_eps);
         HIP_TRY(h, hipMemcpyAsync(h->d_step, &cur, sizeof(cur), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, le);
         src = h->d_eps;
@@ -1947,9 +1945,9 @@ extern "C" mppi_status mppi_rollout_cost(mppi_handle *h, const float *x, const f
     HIP_TRY(h, dx.alloc(h->s)); HIP_TRY(h, dU.alloc(h->HA)); HIP_TRY(h, dc.alloc(h->K_local));
     HIP_TRY(h, dx.up(x, h->s, h->stream)); HIP_TRY(h, dU.up(U, h->HA, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_eps, eps, sizeof(float) * (size_t)h->K_local * h->HA, hipMemcpyHostToDevice, h->stream));
-    if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, h->stream, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
-    else if (h->hc.model_kind == MPPI_MODEL_MLP) HIP_TRY(h, per_a(h, &mppi_unit_a::mlp, h->stream, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p));
-    else HIP_TRY(h, launch_tile(h, h->stream, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
+    if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, h->dC, h->stream, mppi_kev{}, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
+    else if (h->hc.model_kind == MPPI_MODEL_MLP) HIP_TRY(h, per_a(h, &mppi_unit_a::mlp, h->stream, mppi_kev{}, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p));
+    else HIP_TRY(h, launch_tile(h, h->dC, h->stream, SRC_HBM, MODE_COST_ONLY, dx.p, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
     HIP_TRY(h, dc.down(cost_out, h->K_local, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MPPI_OK;
@@ -1971,13 +1969,15 @@ extern "C" mppi_status mppi_update(mppi_handle *h, const float *cost, const floa
     HIP_TRY(h, dU.up(U, HA, h->stream)); HIP_TRY(h, dc.up(cost, K, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_eps, eps, sizeof(float) * (size_t)K * HA, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, ensure_record_layout(h, h->stream, h->nb));
-    if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, h->stream, SRC_HBM, MODE_COSTS_GIVEN, h->d_x, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
-    else HIP_TRY(h, launch_tile(h, h->stream, SRC_HBM, MODE_COSTS_GIVEN, h->d_x, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
+    if (h->is_gen) HIP_TRY(h, mppi_launch_gen(h, h->dC, h->stream, mppi_kev{}, SRC_HBM, MODE_COSTS_GIVEN, h->d_x, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
+    else HIP_TRY(h, launch_tile(h, h->dC, h->stream, SRC_HBM, MODE_COSTS_GIVEN, h->d_x, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
+    h->norm_two_pass = 0; // records made from the GIVEN costs at lambda
     // record = (beta, eta, V); then U' on a scratch copy of U (apply shifts it, so read U_updated)
     unsigned long long step_before = 0;
     HIP_TRY(h, hipMemcpyAsync(&step_before, h->d_step, sizeof(step_before), hipMemcpyDeviceToHost, h->stream));
-    h->norm_two_pass = 0; // records made from the GIVEN costs at lambda
-    HIP_TRY(h, launch_finish(h, h->stream, h->d_part, 1, h->nbp, h->nbp, dU.p, dUn.p, du.p, drec.p, 1));
+    Finish f = own_records(h);
+    f.U_in = dU.p; f.U_out = dUn.p; f.u_out = du.p; f.record_out = drec.p;
+    HIP_TRY(h, launch_finish(h, h->stream, f));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_step, &step_before, sizeof(step_before), hipMemcpyHostToDevice, h->stream)); // stateless call
     hipLaunchKernelGGL(k_weights, dim3((K + 255) / 256), dim3(256), 0, h->stream, h->dC, dc.p, K, drec.p, darg.p, dexp.p, dw.p, (const float *)nullptr);
@@ -2170,15 +2170,11 @@ static mppi_status batch_step(mppi_handle *h, hipStream_t st, const float *x_dev
         return fail(h, MPPI_ERR_UNSUPPORTED, h->is_gen ? "batched step: the Fossen AUV model runs on k_rollout_auv_pc only"
                                                        : "batched step: the horizon exceeds what this producer count serves (tau <= 132 with 3 producers)");
     TraceRange step_range(h, "mppi:batch_step");
-    const bool prof = h->prof_n < h->prof_cap;
-    kernel_events(h, prof); // the dispatches' own begin / end
-    const hipError_t e = h->is_gen ? mppi_launch_batch_auv(h, st, x_dev) : per_a(h, &mppi_unit_a::batch, st, x_dev);
-    h->kev0 = h->kev1 = nullptr;
-    HIP_TRY(h, e);
-    hipEvent_t f0 = prof ? h->ev[4 * h->prof_n + 2] : nullptr, f1 = prof ? h->ev[4 * h->prof_n + 3] : nullptr;
-    HIP_TRY(h, h->is_gen ? mppi_launch_batch_finish_auv(h, st, h->U_cur(), h->U_other(), u_dev, f0, f1)
-                         : per_a(h, &mppi_unit_a::batch_finish, st, (const float *)h->U_cur(), h->U_other(), u_dev, f0, f1));
-    if (prof) { h->prof_stream = st; h->prof_n++; }
+    const ProfSlot p = prof_slot(h); // the dispatches' own begin / end
+    HIP_TRY(h, h->is_gen ? mppi_launch_batch_auv(h, st, p.rollout, x_dev) : per_a(h, &mppi_unit_a::batch, st, p.rollout, x_dev));
+    HIP_TRY(h, h->is_gen ? mppi_launch_batch_finish_auv(h, st, h->U_cur(), h->U_other(), u_dev, p.finish)
+                         : per_a(h, &mppi_unit_a::batch_finish, st, (const float *)h->U_cur(), h->U_other(), u_dev, p.finish));
+    if (p) prof_commit(h, st);
     h->U_advance();
     return MPPI_OK;
 }

@@ -20,7 +20,7 @@ struct mppi_handle {
     hipStream_t stream = nullptr;
     DevConsts hc{};
     DevConsts *dC = nullptr;
-    int norm_two_pass = 0;    // this step's records come from the second pass of the two-pass normalizeCost path (set per step)
+    int norm_two_pass = 0;    // how the last records were made: 1 = from the raw costs at the temperature in d_mm[2] (the weights-only pass of normalizeCost), 0 = at lambda. Written where records are made; read by MPPI_DBG_WEIGHTS and by mppi_shard_finish (the ranks' records)
     int K_global = 0, K_local = 0, k_offset = 0, shard_rank = 0, shard_count = 1;
     int H = 0, s = 0, a = 0, HA = 0;
     int R = 64, nb = 0;   // tile size / record count of the point-mass tile kernels
@@ -41,8 +41,6 @@ struct mppi_handle {
     int normalize = 0;
     int sigma_diag = 0; // Σ and Σ⁻¹ are exactly diagonal (the DIAG kernel instances are bit-identical then)
     int pc_np = 5;      // producer waves per workgroup of k_rollout_pc (chosen by tiles per CU; MPPI_TUNE_PC_PRODUCERS overrides)
-    int pc_pass = 0;    // which pass of k_rollout_pc the next launch_pc is: 0 the step's one pass, 1 / 2 the two passes of normalizeCost (set per launch by mppi_capi.hip)
-    int pc_range_given = 0; // the weights-only pass takes its temperature from d_mm[2] (a K-sharded handle: the ranks agreed on the range) instead of reducing d_tile_mm
     float *d_tile_mm = nullptr; // normalize_cost: every tile's (min, max) cost of the first pass, [2][nbp]
     // diagnostic switches, set only through mppi_set_tuning (the library reads no environment variable)
     int force_tile = 0;   // MPPI_TUNE_FORCE_TILE_KERNEL: the LDS-tile kernel instead of the producer/consumer one (A/B timing)
@@ -81,9 +79,6 @@ struct mppi_handle {
     std::vector<hipEvent_t> ev;   // 4 events per step: rollout begin/end, finish begin/end
     int prof_cap = 0, prof_n = 0; // steps that can be / have been recorded
     hipStream_t prof_stream = nullptr;
-    // when a step is being profiled the dominant kernel is launched with hipExtLaunchKernel, whose start/stop events
-    // carry the dispatch's own begin/end timestamps (what rocprofv3 reports), not the stream-level gaps around it
-    hipEvent_t kev0 = nullptr, kev1 = nullptr;
     std::string no_rollout; // non-empty: why this handle cannot run rollouts (helpers still work)
     int is_gen = 0;         // model_base is AUVModel / NNAUVModel: rollouts run k_rollout_gen
     void *gen = nullptr;    // 13-state AUV family (model AUV / NN_AUV; mppi_launch_gen.hip owns it): constants + device copy
@@ -190,21 +185,27 @@ P mppi_pick_in(K P::*slot, K kern, const std::string &name, dim3 g, dim3 b, size
 template <typename F>
 auto mppi_with_diag(const mppi_handle *h, F &&f) { return h->sigma_diag ? f(std::true_type{}) : f(std::false_type{}); }
 
-// One launch of a rollout kernel on the handle's kernel events (h->kev0 / kev1: the dispatch's own begin / end on a profiled step, else
-// none), after raising the instance's dynamic-LDS ceiling if it needs more than the default.
+// The events of ONE dispatch. When a step is being profiled its dominant kernel is launched with hipExtLaunchKernel, whose start / stop
+// events carry the dispatch's own begin / end timestamps (what rocprofv3 reports), not the stream-level gaps around it; else both are null.
+struct mppi_kev { hipEvent_t begin = nullptr, end = nullptr; };
+// One launch of a rollout kernel on the events `kev`, after raising the instance's dynamic-LDS ceiling if it needs more than the default.
 template <typename... P, typename... Args>
-hipError_t mppi_launch(const mppi_handle *h, void (*kern)(P...), dim3 g, dim3 b, size_t lds, hipStream_t st, Args... args)
+hipError_t mppi_launch(const mppi_handle *h, mppi_kev kev, void (*kern)(P...), dim3 g, dim3 b, size_t lds, hipStream_t st, Args... args)
 {
     if (hipError_t e = mppi_raise_lds_ceiling(reinterpret_cast<const void *>(kern), h->device, lds); e != hipSuccess) return e;
-    hipExtLaunchKernelGGL(kern, g, b, (uint32_t)lds, st, h->kev0, h->kev1, 0, args...);
+    hipExtLaunchKernelGGL(kern, g, b, (uint32_t)lds, st, kev.begin, kev.end, 0, args...);
     return hipGetLastError();
 }
 
-#define MPPI_TILE_PARAMS mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, \
+// What holds for one launch is an argument: `kev`; `consts`, the DevConsts block to run on (h->dC, or a batch member's: mppi_debug_get);
+// `pass` of k_rollout_pc (PC_PASS_PLAIN the step's one pass, PC_PASS_COSTS / _WEIGHTS the two of normalizeCost) and `range_given`: the weights-only
+// pass takes its temperature from d_mm[2] (a K-sharded handle: the ranks agreed on the range; many tiles) instead of reducing d_tile_mm.
+#define MPPI_TILE_PARAMS mppi_handle *h, const DevConsts *consts, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, \
                          const float *eps, float *cost, float *part, float *noise_out
-#define MPPI_MLP_PARAMS mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, \
+#define MPPI_MLP_PARAMS mppi_handle *h, hipStream_t st, mppi_kev kev, int src, int mode, const float *x_dev, const float *U_dev, \
                         const float *eps, float *cost
-#define MPPI_PC_PARAMS mppi_handle *h, hipStream_t st, const float *x_dev
+#define MPPI_PC_PARAMS mppi_handle *h, hipStream_t st, mppi_kev kev, const float *x_dev, int pass, bool range_given
+#define MPPI_BATCH_PARAMS mppi_handle *h, hipStream_t st, mppi_kev kev, const float *x_dev
 // one launch of k_step_pc (mppi_step.hip.h): mode = STEP_FUSE | STEP_ARM bits; the sequence it reads / writes is given explicitly
 // (an armed launch for step n+1 is enqueued before step n's bookkeeping is committed)
 struct mppi_step_launch {
@@ -212,14 +213,14 @@ struct mppi_step_launch {
     const unsigned long long *ugr = nullptr; unsigned utag = 0; unsigned long long step_index = 0; // STEP_PRE: this step's sequence as granules, their tag, the Philox step index
     unsigned long long *ugr_out = nullptr; // STEP_PRE | STEP_FUSE: the next step's granules (the column waves write them)
 };
-#define MPPI_STEP_PARAMS mppi_handle *h, hipStream_t st, const mppi_step_launch *L
-#define MPPI_BATCH_FINISH_PARAMS mppi_handle *h, hipStream_t st, const float *U_in, float *U_out, float *u_dev, hipEvent_t ev0, hipEvent_t ev1
+#define MPPI_STEP_PARAMS mppi_handle *h, hipStream_t st, mppi_kev kev, const mppi_step_launch *L
+#define MPPI_BATCH_FINISH_PARAMS mppi_handle *h, hipStream_t st, const float *U_in, float *U_out, float *u_dev, mppi_kev kev
 // The entry points of the per-a launch units (mppi_launch_{tile,pc,mlp,step,batch}.hip): X(NAME, result, parameters) is defined as
 // mppi_NAME_a1 .. mppi_NAME_a4, one per action dimension, each in its own object file; the *_name entries name what the launch would run.
 // The batched step (mppi_launch_batch.hip): every member's rollout in one launch, every member's finish in another.
 #define MPPI_UNIT_ENTRIES(X)                                                                                                         \
     X(tile, hipError_t, MPPI_TILE_PARAMS) X(pc, hipError_t, MPPI_PC_PARAMS) X(mlp, hipError_t, MPPI_MLP_PARAMS)                       \
-    X(step, hipError_t, MPPI_STEP_PARAMS) X(batch, hipError_t, MPPI_PC_PARAMS) X(batch_finish, hipError_t, MPPI_BATCH_FINISH_PARAMS) \
+    X(step, hipError_t, MPPI_STEP_PARAMS) X(batch, hipError_t, MPPI_BATCH_PARAMS) X(batch_finish, hipError_t, MPPI_BATCH_FINISH_PARAMS) \
     X(tile_name, const char *, const mppi_handle *h, int src, int mode) X(pc_name, const char *, const mppi_handle *h, int pass)      \
     X(mlp_name, const char *, const mppi_handle *h, int src) X(step_name, const char *, const mppi_handle *h, int mode)               \
     X(batch_name, const char *, const mppi_handle *h)
@@ -233,8 +234,8 @@ struct mppi_unit_a { MPPI_UNIT_ENTRIES(MPPI_MEMBER) }; // one row per action dim
 const char *mppi_gen_fill(mppi_handle *h, const mppi_config *cfg); // NULL = ok, else why the config is invalid
 hipError_t mppi_gen_upload(mppi_handle *h);
 void mppi_gen_destroy(mppi_handle *h);
-hipError_t mppi_launch_gen(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, const float *eps,
-                           float *cost, float *part, float *noise_out);
+hipError_t mppi_launch_gen(mppi_handle *h, const DevConsts *consts, hipStream_t st, mppi_kev kev, int src, int mode, const float *x_dev,
+                           const float *U_dev, const float *eps, float *cost, float *part, float *noise_out);
 const char *mppi_gen_name(const mppi_handle *h, int mode); // the instance mppi_launch_gen runs for `mode` without a noise export
 hipError_t mppi_gen_model_step(mppi_handle *h, hipStream_t st, const float *x, int kx, const float *v, int k, float *scratch, float *out_next);
 hipError_t mppi_gen_costs(mppi_handle *h, hipStream_t st, const float *x, const float *u, const float *eps, int k, float *os, float *oa, float *ot);
@@ -243,7 +244,7 @@ hipError_t mppi_gen_e3_terms(mppi_handle *h, hipStream_t st, const float *x, int
 const void *mppi_gen_dev_consts(const mppi_handle *h); // the handle's GenConsts on the device
 // the batched step of the Fossen AUV model (mppi_launch_batch_gen.hip): every member's rollout in one launch (k_rollout_auv_pc_batch),
 // every member's finish in another (k_finish_cols_batch<6>)
-hipError_t mppi_launch_batch_auv(MPPI_PC_PARAMS);
+hipError_t mppi_launch_batch_auv(MPPI_BATCH_PARAMS);
 hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS);
 const char *mppi_batch_auv_name(const mppi_handle *h);
 #define MPPI_CAT_(a, b) a##b

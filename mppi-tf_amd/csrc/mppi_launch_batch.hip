@@ -36,7 +36,7 @@ static BatchPick pick_batch_np(const mppi_handle *h)
 
 static BatchPick pick_batch(const mppi_handle *h) { return h->pc_np == 3 ? pick_batch_np<3>(h) : pick_batch_np<5>(h); }
 
-hipError_t MPPI_CAT(mppi_batch_a, MPPI_UNIT_A)(MPPI_PC_PARAMS)
+hipError_t MPPI_CAT(mppi_batch_a, MPPI_UNIT_A)(MPPI_BATCH_PARAMS)
 {
     const BatchPick p = pick_batch(h);
     const size_t lds = std::max(pc_lds_floats(MPPI_UNIT_A, p.np) * 4, (size_t)h->pc_lds_min);
@@ -44,7 +44,7 @@ hipError_t MPPI_CAT(mppi_batch_a, MPPI_UNIT_A)(MPPI_PC_PARAMS)
     const int tiles = nb * h->batch;
     const PcBatchArgs bt{nb, h->HA + h->a, h->nbp * (2 + h->HA)};
     // roles and head starts as a lone handle's, enabled by the TOTAL tile count: the whole grid must be resident in one round
-    return mppi_launch(h, p.kern, dim3(tiles), dim3(64 * (p.np + 1)), lds, st, h->dC, x_dev, h->U_cur(), h->d_step, h->d_cost, h->d_part, 1,
+    return mppi_launch(h, kev, p.kern, dim3(tiles), dim3(64 * (p.np + 1)), lds, st, h->dC, x_dev, h->U_cur(), h->d_step, h->d_cost, h->d_part, 1,
                        h->nbp, mppi_pc_balance(h, MPPI_UNIT_A, p.nslot, tiles), (float *)nullptr, (float *)nullptr, bt);
 }
 
@@ -53,7 +53,7 @@ const char *MPPI_CAT(mppi_batch_name_a, MPPI_UNIT_A)(const mppi_handle *h) { ret
 // the finish of every member: one workgroup per (member, column); reads U_in, writes U_out and u_dev [B][a]
 hipError_t MPPI_CAT(mppi_batch_finish_a, MPPI_UNIT_A)(MPPI_BATCH_FINISH_PARAMS)
 {
-    hipExtLaunchKernelGGL(k_finish_cols_batch<MPPI_UNIT_A>, dim3(h->HA * h->batch), dim3(kThreads), 0, st, ev0, ev1, 0, (const float *)h->d_part, h->nbp,
+    hipExtLaunchKernelGGL(k_finish_cols_batch<MPPI_UNIT_A>, dim3(h->HA * h->batch), dim3(kThreads), 0, st, kev.begin, kev.end, 0, (const float *)h->d_part, h->nbp,
                           h->nbp, h->HA, h->nbp * (2 + h->HA), (const DevConsts *)h->dC, U_in, U_out, h->HA + h->a, u_dev, h->d_step, h->d_dbg,
                           (const float *)h->d_clip);
     return hipGetLastError();

@@ -223,16 +223,16 @@ static GenPick pick_gen(const mppi_handle *h, int mode, bool noise_out)
 const char *mppi_gen_name(const mppi_handle *h, int mode) { return pick_gen(h, mode, false).name; }
 
 // rollouts of a 13-state handle
-hipError_t mppi_launch_gen(mppi_handle *h, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev, const float *eps,
-                           float *cost, float *part, float *noise_out)
+hipError_t mppi_launch_gen(mppi_handle *h, const DevConsts *consts, hipStream_t st, mppi_kev kev, int src, int mode, const float *x_dev,
+                           const float *U_dev, const float *eps, float *cost, float *part, float *noise_out)
 {
     const GenPick p = pick_gen(h, mode, noise_out != nullptr);
     const GenConsts *G = gs(h)->dG;
-    if (p.one) return mppi_launch(h, p.one, p.g, p.b, 0, st, h->dC, G, h->dM, h->small_args, x_dev, U_dev, eps, h->d_step, cost, part, noise_out, src, mode, 1, h->nbp);
-    if (p.mfma) return mppi_launch(h, p.mfma, p.g, p.b, 0, st, h->dC, G, h->dM, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp);
+    if (p.one) return mppi_launch(h, kev, p.one, p.g, p.b, 0, st, consts, G, h->dM, h->small_args, x_dev, U_dev, eps, h->d_step, cost, part, noise_out, src, mode, 1, h->nbp);
+    if (p.mfma) return mppi_launch(h, kev, p.mfma, p.g, p.b, 0, st, consts, G, h->dM, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp);
     const int balance = mppi_two_tile_balance(h, (int)p.g.x);
-    if (p.pipe) return mppi_launch(h, p.pipe, p.g, p.b, 0, st, h->dC, G, h->dM, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
-    return mppi_launch(h, p.auv, p.g, p.b, 0, st, h->dC, G, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
+    if (p.pipe) return mppi_launch(h, kev, p.pipe, p.g, p.b, 0, st, consts, G, h->dM, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
+    return mppi_launch(h, kev, p.auv, p.g, p.b, 0, st, consts, G, x_dev, U_dev, eps, h->d_step, cost, part, src, mode, 1, h->nbp, h->nb, balance);
 }
 
 // NNAUVModel.build_step_graph in the reference's plain order (mul and add rounded separately, input index ascending, division by

@@ -72,12 +72,12 @@ hipError_t MPPI_CAT(mppi_mlp_a, MPPI_UNIT_A)(MPPI_MLP_PARAMS)
 {
     if (mode != MODE_ROLLOUT && mode != MODE_COST_ONLY) return hipErrorInvalidValue;
     const MlpPick p = pick_mlp<MPPI_UNIT_A>(h, src);
-    if (p.plain) return mppi_launch(h, p.plain, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
+    if (p.plain) return mppi_launch(h, kev, p.plain, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
     if (p.pipe)
-        return mppi_launch(h, p.pipe, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp, h->nb_mlp,
+        return mppi_launch(h, kev, p.pipe, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp, h->nb_mlp,
                            mppi_two_tile_balance(h, (int)p.g.x));
-    if (p.small) return mppi_launch(h, p.small, p.g, p.b, p.lds, st, h->dC, h->dM, h->small_args, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
-    if (p.nosrc) return mppi_launch(h, p.nosrc, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, mode, 1, h->nbp);
+    if (p.small) return mppi_launch(h, kev, p.small, p.g, p.b, p.lds, st, h->dC, h->dM, h->small_args, x_dev, U_dev, eps, h->d_step, cost, h->d_part, src, mode, 1, h->nbp);
+    if (p.nosrc) return mppi_launch(h, kev, p.nosrc, p.g, p.b, p.lds, st, h->dC, h->dM, x_dev, U_dev, eps, h->d_step, cost, h->d_part, mode, 1, h->nbp);
     return hipErrorInvalidValue;
 }
 

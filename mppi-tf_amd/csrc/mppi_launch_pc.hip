@@ -17,7 +17,7 @@ static PcPick pc_inst()
     return {k_rollout_pc<A, NP, NSLOT, DIAG, COST, PASS>, name.c_str(), NP, NSLOT};
 }
 
-// pass: PC_PASS_PLAIN, or the two passes of normalizeCost (mppi_capi.hip sets h->pc_pass around its launches). The weights-only pass
+// pass: PC_PASS_PLAIN, or the two passes of normalizeCost (an argument of the launch). The weights-only pass
 // evaluates no state cost: ONE instance (the diagonal-Q one) serves every cost form.
 template <int A, int NP, int NSLOT, bool DIAG, int COST>
 static PcPick pc_pass(int pass)
@@ -52,12 +52,12 @@ static PcPick pick_pc(const mppi_handle *h, int pass) { return h->pc_np == 3 ? p
 
 hipError_t MPPI_CAT(mppi_pc_a, MPPI_UNIT_A)(MPPI_PC_PARAMS)
 {
-    const PcPick p = pick_pc(h, h->pc_pass);
+    const PcPick p = pick_pc(h, pass);
     const size_t lds = std::max(pc_lds_floats(MPPI_UNIT_A, p.np) * 4, (size_t)h->pc_lds_min);
     const int nb = (h->K_local + 63) / 64;
     // tile records go out column-major ([2+HA][nb]): the finish kernel reads one column per workgroup
-    float *tile_mm = (h->pc_pass == PC_PASS_WEIGHTS && h->pc_range_given) ? nullptr : h->d_tile_mm; // (sharded: the agreed range is already in d_mm)
-    return mppi_launch(h, p.kern, dim3(nb), dim3(64 * (p.np + 1)), lds, st, h->dC, x_dev, h->U_cur(), h->d_step, h->d_cost, h->d_part, 1, h->nbp,
+    float *tile_mm = (pass == PC_PASS_WEIGHTS && range_given) ? nullptr : h->d_tile_mm; // (sharded: the agreed range is already in d_mm)
+    return mppi_launch(h, kev, p.kern, dim3(nb), dim3(64 * (p.np + 1)), lds, st, h->dC, x_dev, h->U_cur(), h->d_step, h->d_cost, h->d_part, 1, h->nbp,
                        mppi_pc_balance(h, MPPI_UNIT_A, p.nslot, nb), tile_mm, h->d_mm);
 }
 

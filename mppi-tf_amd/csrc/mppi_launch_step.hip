@@ -68,7 +68,7 @@ hipError_t MPPI_CAT(mppi_step_a, MPPI_UNIT_A)(MPPI_STEP_PARAMS)
     sa.neg_inv_lambda = h->hc.neg_inv_lambda; sa.a = h->a; sa.HA = h->HA;
     sa.ugr = L->ugr; sa.utag = L->utag; sa.step_index = L->step_index; sa.cu_ctr = h->d_cu_ctr; sa.ugr_out = L->ugr_out;
     if (PRE) sa.hard_ticks = 20ll * 100000ll; // 20 ms: a sequence that has not come by then never will (sticky error word)
-    return mppi_launch(h, p.kern, dim3(nb + ncw), dim3(64 * NW), lds, st, h->dC, L->x_dev, L->U_in, h->d_step, h->d_cost, h->d_part, 1, h->nbp,
+    return mppi_launch(h, kev, p.kern, dim3(nb + ncw), dim3(64 * NW), lds, st, h->dC, L->x_dev, L->U_in, h->d_step, h->d_cost, h->d_part, 1, h->nbp,
                        mppi_pc_balance(h, MPPI_UNIT_A, p.nslot, nb), sa);
 }
 

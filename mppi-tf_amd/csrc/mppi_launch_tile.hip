@@ -49,7 +49,7 @@ hipError_t MPPI_CAT(mppi_tile_a, MPPI_UNIT_A)(MPPI_TILE_PARAMS)
     const TilePick p = pick_tile(h, src, mode);
     if (!p.kern) return hipErrorInvalidValue;
     if (hipError_t e = mppi_raise_lds_ceiling(reinterpret_cast<const void *>(p.kern), h->device, h->tile_lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(p.kern, dim3(h->nb), dim3(kThreads), h->tile_lds, st, h->dC, x_dev, U_dev, eps, h->d_step, cost, part, noise_out, 1, h->nbp);
+    hipLaunchKernelGGL(p.kern, dim3(h->nb), dim3(kThreads), h->tile_lds, st, consts, x_dev, U_dev, eps, h->d_step, cost, part, noise_out, 1, h->nbp);
     return hipGetLastError();
 }
 

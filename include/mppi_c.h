@@ -280,7 +280,10 @@ mppi_status mppi_next_device(mppi_handle *h, const float *x_dev, float *u_dev, v
 /* Sharded step, phase 1: rollouts + local soft-min of this shard -> record_dev[record_size]. */
 mppi_status mppi_shard_partial(mppi_handle *h, const float *x_dev, float *record_dev, void *stream);
 /* Sharded step, phase 2: combine n_records records (all shards, rank order — the result of an
- * all-gather) with r_g = exp(-(beta_g-beta)/λ), apply U' = U + V/η, emit u_dev[a], shift U. */
+ * all-gather) with r_g = exp(-(beta_g-beta)/λ), apply U' = U + V/η, emit u_dev[a], shift U.
+ * More than 1024 records are first folded 16:1 in the handle's scratch, which holds ceil(T/16) records for the handle's own T
+ * record slots (its tiles, padded): n_records must be <= 1024, or ceil(n_records/16) <= ceil(T/16). Any other count is refused
+ * with MPPI_ERR_INVALID_ARG before anything is launched. */
 mppi_status mppi_shard_finish(mppi_handle *h, const float *records_dev, int n_records, float *u_dev, void *stream);
 /* normalize_cost on a sharded handle (controller_base.py:468-474: c' = (c - min c)/(max c - min c) over ALL K samples). Phase 1
  * splits in two around a second, 2-float exchange:

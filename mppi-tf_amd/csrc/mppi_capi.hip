@@ -714,14 +714,16 @@ static hipError_t launch_finish(mppi_handle *h, hipStream_t st, Finish f)
     // a profiled step = the rollout kernel + the finish that applies the update
     TraceRange tr(h, f.apply ? "mppi:finish" : "mppi:record");
     const ProfSlot p = f.apply ? prof_slot(h) : ProfSlot{};
-    float *out = h->d_part2;
+    // The levels alternate between the two scratch buffers, so that no level reads the buffer it writes: level 1 fills d_part2
+    // (ceil(nbp/16) records), level 2 d_part3 (1/16 of that), level 3 d_part2 again (1/256 of it), ...
+    float *out = h->d_part2, *other = h->d_part3;
     while (f.n > 1024) {
         const int ng = (f.n + kGroup - 1) / kGroup;
         hipLaunchKernelGGL(k_combine_group, dim3(ng), dim3(kThreads), 0, st, f.recs, f.sb, f.sc, f.n, h->HA, h->hc.neg_inv_lambda, out, f.nil_dev);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         f.recs = out; f.sb = 2 + h->HA; f.sc = 1; f.n = ng;
-        out = h->d_part3;
+        std::swap(out, other);
     }
     const mppi_kev kev = p.finish; // profiled: the finish kernel's own dispatch begin/end (hipExtLaunchKernel events), like the rollout kernel's
     if (f.xchg)
@@ -1231,6 +1233,10 @@ extern "C" mppi_status mppi_shard_finish(mppi_handle *h, const float *records_de
 {
     MPPI_NOT_BATCH(h, "mppi_shard_finish");
     if (!h || !records_dev || !u_dev || n_records <= 0) return h ? fail(h, MPPI_ERR_INVALID_ARG, "bad records/u pointer or count") : MPPI_ERR_INVALID_ARG;
+    // more than 1024 records are folded 16:1 into the handle's scratch, which is sized for its own ceil(nbp/16) groups
+    if (n_records > 1024 && (n_records + kGroup - 1) / kGroup > (h->nbp + kGroup - 1) / kGroup)
+        return fail(h, MPPI_ERR_INVALID_ARG, "mppi_shard_finish: " + std::to_string(n_records) + " records fold into more groups than this handle's scratch holds (" +
+                                                 std::to_string((h->nbp + kGroup - 1) / kGroup) + "): at most 1024 records, or a handle with at least as many tiles");
     MPPI_ENTER(h);
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     Finish f = own_records(h);

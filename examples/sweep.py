@@ -4,10 +4,15 @@ BatchHandle with its own lambda, upsilon, gamma and Sigma (BatchHandle's lams / 
 same two launches. This is the grid the reference sweeps with one process per point (5 x 4 x 5 x 3 = 300 runs of 300 steps):
     python examples/sweep.py                                   # that grid, 300 steps, the point-mass static task
     python examples/sweep.py --lams 0.05 0.2 --upsilons 1 2 --gammas 0.1 --noises 0.1 0.2 -s 5
+    python examples/sweep.py --on-device                       # the whole closed loop as ONE call (BatchHandle.run_episode)
 The controller uses the Python action-cost form (gamma, upsilon; ACTION_COST_PY) with upsilon scaling the noise (upsilon_scales_noise).
 Plant and controller are the point mass of examples/config/point_mass3d.yaml on the static task examples/config/static_task3d.yaml; noise
 n means Sigma = n I. Every member draws its noise from the same Philox key (--seed), as every run of the reference's sweep does. Prints the
 final distance to the goal of every grid point.
+Without --on-device every step is hb.next(X): a host-synchronous call, u to the host, the numpy plant below, x back. With it the grid's
+steps run as one run_episode call: the controller's own point-mass model is the plant, on the device, and the trajectory comes back once.
+The two modes print the same table in different digits: the numpy plant holds dt^2/2m rounded once from double, the model divides in
+fp32 (one ulp apart), and the closed loop at these temperatures amplifies that to the size of the noise within twenty steps.
 The reference sweeps its ellipse task; a batch refuses the 2D ellipse cost (ElipseCost), so this sweep runs the static task."""
 import argparse
 import itertools
@@ -46,6 +51,7 @@ def main():
     ap.add_argument("-s", "--steps", type=int, default=300)
     ap.add_argument("--samples", type=int, default=None, help="samples per member (default: the config's)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--on-device", action="store_true", help="run all steps as one BatchHandle.run_episode call (the model is the plant)")
     o = ap.parse_args()
     with open(o.config) as fh:
         conf = yaml.safe_load(fh)
@@ -64,8 +70,11 @@ def main():
                        sigmas=[g[3] * np.eye(a, dtype=np.float32) for g in grid])
     X = np.zeros((n, s), np.float32)
     t0 = time.perf_counter()
-    for _ in range(o.steps):
-        X = plant(X, hb.next(X), dt, mass)
+    if o.on_device:
+        X = hb.run_episode(X, o.steps)[0][-1]
+    else:
+        for _ in range(o.steps):
+            X = plant(X, hb.next(X), dt, mass)
     wall = time.perf_counter() - t0
     dist = np.linalg.norm(X[:, 0::2] - goal[0::2], axis=1)
     print("%8s %8s %8s %8s  %s" % ("lambda", "upsilon", "gamma", "noise", "final goal distance"))

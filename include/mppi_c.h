@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define MPPI_ABI_VERSION 5 /* 5: MPPI_TUNE_FUSED_STEP / _ARMED_US / _ARMED_ALWAYS / _PRELAUNCH (no entry point changed); 4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
+#define MPPI_ABI_VERSION 5 /* 5: MPPI_TUNE_FUSED_STEP / _ARMED_US / _ARMED_ALWAYS / _PRELAUNCH (no entry point changed), mppi_run_episode / mppi_batch_run_episode
+                              (added; no entry point changed); 4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
                               _load / _peek, MPPI_TUNE_TRACE (roctx ranges); mppi_set_mlp orders against the last step's stream;
                               3: the 13-state AUV family (MPPI_MODEL_AUV / _NN_AUV, mppi_auv_desc), StaticQuatCost / ElipseCost3D state costs,
                               mppi_auv_pieces, the learner (mppi_learner_*); 2: state_cost_kind / ellipse, transition log, tuning */
@@ -450,6 +451,30 @@ mppi_status mppi_batch_set_action_sequences(mppi_handle *h, const float *U, int 
 /* mppi_debug_get of ONE member (MPPI_DBG_*, the sizes of a lone handle) with the member's own constants: MPPI_DBG_WEIGHTS at its lambda,
  * MPPI_DBG_NOISE regenerated from its Philox key and sigma */
 mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what, float *out, size_t n);
+
+/* ---- closed-loop episodes: n_steps control steps on the device, the handle's own model as the plant ---------------------------------
+ * For t = 0 .. n_steps-1, per member:
+ *   1. goals given: goal <- goals[t] (the effect of mppi_set_goal / mppi_batch_set_goals before the step);
+ *   2. C[t] = the state cost of x_t under that goal (mppi_state_cost's value);
+ *   3. U[t] = the control of one ordinary step from x_t: what mppi_next_device on the handle's own stream runs (one launch, two, or the
+ *      normalize_cost passes; action limits and the sequence filter apply), never the pre-launched or an armed step; a batch: its batched step;
+ *   4. x_{t+1} = model(x_t, U[t]), bit for bit mppi_model_step's out_next;
+ *   5. disturbance given: x_{t+1} = x_{t+1} + w_t, a raw fp32 add per component (keep a 13-state model's quaternion entries at zero);
+ *   6. X[0] = x0, X[t+1] = x_{t+1}.
+ * All steps are enqueued on the handle's own stream without a host wait between them; the call returns after one synchronisation. Behind
+ * every control step ONE more launch closes the loop (a learned model: two). Afterwards the handle is where the host loop "set goal, next,
+ * model_step" repeated n_steps times leaves it: the sequence warm-started and shifted n_steps times, the step counter advanced by n_steps,
+ * the goal equal to the last row of goals; a second call continues where the first stopped. The transition log is not written: X, U and
+ * C are the episode's log. Host pointers; goals, disturbance and each output may be NULL.
+ * MPPI_ERR_INVALID_ARG: n_steps < 1, a wrong n_x, x0 NULL, a sharded handle (as mppi_next_device), mppi_batch_run_episode on a lone
+ * handle. MPPI_ERR_UNSUPPORTED: mppi_run_episode on a batched handle, a handle that runs no rollouts. Nothing is enqueued before a refusal. */
+/* lone handle: x0[s] (n_x = s_dim), goals / disturbance [n_steps, s] -> X[n_steps+1, s], U[n_steps, a], C[n_steps] */
+mppi_status mppi_run_episode(mppi_handle *h, const float *x0, int n_x, int n_steps, const float *goals, const float *disturbance,
+                             float *X_out, float *U_out, float *C_out);
+/* batched handle, a member axis after the step axis: x0[B, s] (n_x = B*s_dim), goals / disturbance [n_steps, B, s] ->
+ * X[n_steps+1, B, s], U[n_steps, B, a], C[n_steps, B] */
+mppi_status mppi_batch_run_episode(mppi_handle *h, const float *x0, int n_x, int n_steps, const float *goals, const float *disturbance,
+                                   float *X_out, float *U_out, float *C_out);
 
 /* ---- the learner of the learned model_base (replaces LearnerBase.train / _train_step, learners/learner_base.py:324-358,
  * 469-496; train_all :146-153) --------------------------------------------------------------------------------------------

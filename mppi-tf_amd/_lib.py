@@ -133,6 +133,9 @@ SIGNATURES = {
     "mppi_batch_get_action_sequences": (C.c_int, [_H, FP, C.c_int]),
     "mppi_batch_set_action_sequences": (C.c_int, [_H, FP, C.c_int]),
     "mppi_batch_debug_get": (C.c_int, [_H, C.c_int, C.c_int, FP, C.c_size_t]),
+    # closed-loop episodes on the device (Handle.run_episode, BatchHandle.run_episode)
+    "mppi_run_episode": (C.c_int, [_H, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
+    "mppi_batch_run_episode": (C.c_int, [_H, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
     # the learner (LearnerBase.train / _train_step)
     "mppi_learner_create": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(FP), C.POINTER(FP), C.c_int, C.POINTER(_H)]),
     "mppi_learner_destroy": (None, [_H]),
@@ -334,6 +337,28 @@ class _HandleBase:
     def synchronize(self):
         self._check(self.lib.mppi_synchronize(self.h))
 
+    def _run_episode(self, name, lead, x0, n_steps, goals, disturbance):
+        """n_steps closed-loop steps through the entry point `name` (mppi_run_episode / mppi_batch_run_episode); lead = () for a lone handle, (n,) for a batch:
+        x0 [*lead, s], goals / disturbance [n_steps, *lead, s] or None -> (X [n_steps+1, *lead, s], U [n_steps, *lead, a], C [n_steps, *lead]).
+        Shapes are checked here, before the library is called: a bad one raises ValueError."""
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be >= 1, not %d" % n_steps)
+
+        def shaped(name, v, shape):
+            v = np.asarray(v, dtype=np.float32)
+            if v.shape != shape:
+                raise ValueError("%s must have shape %s, not %s" % (name, shape, v.shape))
+            return np.ascontiguousarray(v)
+        x0 = shaped("x0", x0, (*lead, self.s))
+        goals = None if goals is None else shaped("goals", goals, (n_steps, *lead, self.s))
+        disturbance = None if disturbance is None else shaped("disturbance", disturbance, (n_steps, *lead, self.s))
+        X = np.zeros((n_steps + 1, *lead, self.s), np.float32)
+        U = np.zeros((n_steps, *lead, self.a), np.float32)
+        Cs = np.zeros((n_steps, *lead), np.float32)
+        self._check(getattr(self.lib, name)(self.h, fp(x0), x0.size, n_steps, fp(goals), fp(disturbance), fp(X), fp(U), fp(Cs)))
+        return X, U, Cs
+
     def rollout_kernel_name(self):
         buf = C.create_string_buffer(128)
         self._check(self.lib.mppi_rollout_kernel_name(self.h, buf, 128))
@@ -443,6 +468,13 @@ class Handle(_HandleBase):
         u = np.zeros(self.a, np.float32)
         self._check(self.lib.mppi_next_with_noise(self.h, fp(x), x.size, fp(eps), eps.size, fp(u), u.size))
         return u
+
+    def run_episode(self, x0, n_steps, goals=None, disturbance=None):
+        """mppi_run_episode: n_steps control steps on the device with the handle's own model as the plant, no host round trip between them.
+        x0 [s]; goals [n_steps, s]: the goal in force at step t; disturbance [n_steps, s]: w_t added to the plant's x'
+        -> (X [n_steps+1, s] the realised trajectory, U [n_steps, a] the controls, C [n_steps] the state cost of x_t under step t's goal).
+        The handle ends where the host loop set_goal, next, model_next leaves it."""
+        return self._run_episode("mppi_run_episode", (), x0, n_steps, goals, disturbance)
 
     def save_next(self, x_next):
         x = f32(x_next).ravel()
@@ -683,6 +715,11 @@ class BatchHandle(_HandleBase):
     def next_device(self, x_ptr, u_ptr, stream=None):
         """x_ptr [n, s_dim] -> u_ptr [n, a_dim], device pointers; enqueue only (stream: Handle.next_device's convention)"""
         self._check(self.lib.mppi_batch_next_device(self.h, x_ptr, u_ptr, self._stream(stream)))
+
+    def run_episode(self, X0, n_steps, goals=None, disturbance=None):
+        """mppi_batch_run_episode: Handle.run_episode for every member at once. X0 [n, s]; goals / disturbance [n_steps, n, s]
+        -> (X [n_steps+1, n, s], U [n_steps, n, a], C [n_steps, n]); member m's slices are its lone handle's episode."""
+        return self._run_episode("mppi_batch_run_episode", (self.n,), X0, n_steps, goals, disturbance)
 
     def get_action_sequences(self):
         U = np.zeros((self.n, self.tau, self.a), np.float32)

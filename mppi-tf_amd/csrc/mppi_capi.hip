@@ -237,7 +237,7 @@ extern "C" void mppi_destroy(mppi_handle *h)
                      h->d_record, h->d_dbg, h->d_mm, h->d_eps, h->d_recs, h->d_range, h->d_tile_mm};
     for (float *p : bufs) if (p) (void)hipFree(p);
     if (h->d_step) (void)hipFree(h->d_step);
-    for (float *p : {h->d_bx, h->d_bu}) if (p) (void)hipFree(p);
+    for (float *p : {h->d_bx, h->d_bu, h->d_ep}) if (p) (void)hipFree(p);
     if (h->dM) (void)hipFree(h->dM);
     if (h->d_mlp_w) (void)hipFree(h->d_mlp_w);
     if (h->dC) (void)hipFree(h->dC);
@@ -2232,4 +2232,88 @@ extern "C" mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what
     if (!out) return fail(h, MPPI_ERR_INVALID_ARG, "out is NULL");
     if (member < 0 || member >= h->batch) return fail(h, MPPI_ERR_INVALID_ARG, "member out of range");
     return debug_get(h, member, what, out, n);
+}
+
+// ---- closed-loop episodes (include/mppi_c.h): n_steps control steps with the handle's own model as the plant, on the handle's stream, no host
+// wait between the steps. Step t is the plain step (plain_step / batch_step: never the pre-launched or an armed one — x of step t + 1 depends
+// on u of step t) reading row t of the trajectory and writing row t of the control log, then ONE launch (mppi_episode.hip) that writes C[t],
+// row t + 1 of the trajectory and the next goal. A learned model spends one launch more on its model-step kernel.
+static mppi_status ensure_episode_staging(mppi_handle *h, size_t floats)
+{
+    if (floats <= h->ep_cap) return MPPI_OK;
+    if (h->d_ep) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(h->d_ep)); h->d_ep = nullptr; h->ep_cap = 0; }
+    HIP_TRY(h, hipMalloc((void **)&h->d_ep, sizeof(float) * floats));
+    h->ep_cap = floats;
+    return MPPI_OK;
+}
+
+static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0, int n_x, int n_steps, const float *goals, const float *disturbance,
+                               float *X_out, float *U_out, float *C_out)
+{
+    const int B = members(h), s = h->s, a = h->a;
+    const std::string who = std::string(name) + ": ";
+    if (!x0 || n_x != B * s) return fail(h, MPPI_ERR_INVALID_ARG, who + (h->batch ? "x0 must hold n * s_dim floats" : "x0 must hold s_dim floats"));
+    if (n_steps < 1 || n_steps > (1 << 24)) return fail(h, MPPI_ERR_INVALID_ARG, who + "n_steps must be in [1, 2^24]");
+    if (h->shard_count != 1) return fail(h, MPPI_ERR_INVALID_ARG, "sharded handle: use mppi_shard_partial / mppi_shard_finish");
+    if (!h->no_rollout.empty()) return fail(h, MPPI_ERR_UNSUPPORTED, h->no_rollout);
+    if (h->batch && (h->is_gen ? !auv_batch_eligible(h) : !pc_eligible(h)))
+        return fail(h, MPPI_ERR_UNSUPPORTED, h->is_gen ? "batched step: the Fossen AUV model runs on k_rollout_auv_pc only"
+                                                       : "batched step: the horizon exceeds what this producer count serves (tau <= 132 with 3 producers)");
+    MPPI_ENTER(h);
+    const size_t n = (size_t)n_steps, xs = (size_t)B * s, us = (size_t)B * a;
+    const size_t kScratch = 2 * kHid; // k_mlp_step_ref: 2 * 256 floats per sample; k_nnauv_step_ref: 128
+    const size_t oX = 0, oU = oX + (n + 1) * xs, oC = oU + n * us, oG = oC + n * B, oW = oG + (goals ? n * xs : 0), oS = oW + (disturbance ? n * xs : 0);
+    if (mppi_status st = ensure_episode_staging(h, oS + kScratch); st != MPPI_OK) return st;
+    float *dX = h->d_ep + oX, *dU = h->d_ep + oU, *dC = h->d_ep + oC, *dG = goals ? h->d_ep + oG : nullptr, *dW = disturbance ? h->d_ep + oW : nullptr;
+    float *scratch = h->d_ep + oS;
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(dX, x0, sizeof(float) * xs, hipMemcpyHostToDevice, st));
+    if (dW) HIP_TRY(h, hipMemcpyAsync(dW, disturbance, sizeof(float) * n * xs, hipMemcpyHostToDevice, st));
+    if (dG) {
+        // goal <- goals[0], as mppi_set_goal / mppi_batch_set_goals before the first step; the later rows are stored by the episode kernel
+        HIP_TRY(h, hipMemcpyAsync(dG, goals, sizeof(float) * n * xs, hipMemcpyHostToDevice, st));
+        const size_t row = sizeof(float) * s;
+        HIP_TRY(h, hipMemcpy2DAsync((char *)h->dC + offsetof(DevConsts, goal), sizeof(DevConsts), dG, row, row, B, hipMemcpyDeviceToDevice, st));
+    }
+    const int mk = h->hc.model_kind;
+    const bool learned = mk == MPPI_MODEL_MLP || mk == MPPI_MODEL_NN_AUV || mk == MPPI_MODEL_NN_AUV_SPEED;
+    for (int t = 0; t < n_steps; ++t) {
+        const float *x_t = dX + (size_t)t * xs;
+        float *u_t = dU + (size_t)t * us, *x_next = dX + (size_t)(t + 1) * xs;
+        if (h->batch) {
+            if (mppi_status s_ = batch_step(h, st, x_t, u_t); s_ != MPPI_OK) return s_;
+        } else {
+            TraceRange step_range(h, "mppi:step");
+            if (mppi_status s_ = plain_step(h, st, SRC_PHILOX, x_t, nullptr, u_t); s_ != MPPI_OK) return s_;
+        }
+        TraceRange plant_range(h, "mppi:plant");
+        if (mk == MPPI_MODEL_MLP) {
+            hipLaunchKernelGGL(k_mlp_step_ref, dim3(1), dim3(64), 0, st, h->dC, h->dM, x_t, 1, (const float *)u_t, 1, scratch, x_next);
+            HIP_TRY(h, hipGetLastError());
+        } else if (learned) HIP_TRY(h, mppi_gen_model_step(h, st, x_t, 1, u_t, 1, scratch, x_next));
+        const mppi_episode_tail e{x_t, u_t, dW ? dW + (size_t)t * xs : nullptr, (dG && t + 1 < n_steps) ? dG + (size_t)(t + 1) * xs : nullptr,
+                                  dC + (size_t)t * B, x_next, learned ? 0 : 1};
+        HIP_TRY(h, mppi_launch_episode_tail(h, st, e));
+    }
+    if (X_out) HIP_TRY(h, hipMemcpyAsync(X_out, dX, sizeof(float) * (n + 1) * xs, hipMemcpyDeviceToHost, st));
+    if (U_out) HIP_TRY(h, hipMemcpyAsync(U_out, dU, sizeof(float) * n * us, hipMemcpyDeviceToHost, st));
+    if (C_out) HIP_TRY(h, hipMemcpyAsync(C_out, dC, sizeof(float) * n * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (goals) for (int i = 0; i < s; ++i) h->hc.goal[i] = goals[(n - 1) * xs + i]; // the host mirror (member 0's)
+    return MPPI_OK;
+}
+
+extern "C" mppi_status mppi_run_episode(mppi_handle *h, const float *x0, int n_x, int n_steps, const float *goals, const float *disturbance,
+                                        float *X_out, float *U_out, float *C_out)
+{
+    if (!h) return MPPI_ERR_INVALID_ARG;
+    if (h->batch) return fail(h, MPPI_ERR_UNSUPPORTED, "mppi_run_episode: a batched handle runs its episodes through mppi_batch_run_episode");
+    return run_episode(h, "mppi_run_episode", x0, n_x, n_steps, goals, disturbance, X_out, U_out, C_out);
+}
+
+extern "C" mppi_status mppi_batch_run_episode(mppi_handle *h, const float *x0, int n_x, int n_steps, const float *goals, const float *disturbance,
+                                              float *X_out, float *U_out, float *C_out)
+{
+    MPPI_BATCH_ONLY(h);
+    return run_episode(h, "mppi_batch_run_episode", x0, n_x, n_steps, goals, disturbance, X_out, U_out, C_out);
 }

@@ -1,7 +1,8 @@
 // mppi_handle.hip.h — host-side state of one controller (mppi_handle) and the launchers of the rollout kernels.
 // The library is several translation units compiled in parallel (mppi-tf_amd/build.py): mppi_capi.hip holds the C-ABI,
 // mppi_launch_tile.hip / _pc.hip / _mlp.hip / _batch.hip instantiate one kernel family each for ONE action dimension per object
-// (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step. This header is
+// (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step, mppi_episode.hip the plant of a closed-loop
+// episode. This header is
 // what they share.
 #pragma once
 #include "mppi_kernels.hip.h"
@@ -130,6 +131,10 @@ struct mppi_handle {
     // the two batched launches (mppi_launch_batch.hip; the Fossen AUV model: mppi_launch_batch_gen.hip).
     int batch = 0;
     float *d_bx = nullptr, *d_bu = nullptr;
+    // a closed-loop episode's staging (mppi_run_episode / mppi_batch_run_episode): X | U | C | goals | disturbance | model-step scratch, one
+    // allocation that grows on demand
+    float *d_ep = nullptr;
+    size_t ep_cap = 0; // floats
     size_t xchg_step_slots() const { return (size_t)2 * HA * shard_count * 3; }
     size_t xchg_inbox_bytes() const { return sizeof(unsigned long long) * (xchg_step_slots() + (size_t)2 * shard_count); }
 };
@@ -247,5 +252,15 @@ const void *mppi_gen_dev_consts(const mppi_handle *h); // the handle's GenConsts
 hipError_t mppi_launch_batch_auv(MPPI_BATCH_PARAMS);
 hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS);
 const char *mppi_batch_auv_name(const mppi_handle *h);
+// The plant of a closed-loop episode (mppi_episode.hip): ONE launch behind a control step serves every member. Member m: C[t] = the state
+// cost of x_t under the goal in force; x_{t+1} = model(x_t, u_t) (+ w_t) into the trajectory's next row, which is the next step's x_dev; the
+// goal of step t + 1 into the member's DevConsts.goal. model = 0 (a learned model): an existing model-step kernel has written x_next already.
+struct mppi_episode_tail {
+    const float *x, *u;         // x_t [B][s], u_t [B][a]
+    const float *w, *goal_next; // w_t [B][s] / goal_{t+1} [B][s], or NULL
+    float *cost, *x_next;       // C[t] [B], x_{t+1} [B][s]
+    int model;
+};
+hipError_t mppi_launch_episode_tail(mppi_handle *h, hipStream_t st, const mppi_episode_tail &e);
 #define MPPI_CAT_(a, b) a##b
 #define MPPI_CAT(a, b) MPPI_CAT_(a, b)

@@ -1,0 +1,103 @@
+"""A closed loop on the device against the host loop it replaces, at one grid, in one process. Per control step of the whole batch:
+  (a) host:    the loop of examples/sweep.py without --on-device: hb.next(X) (host-synchronous), u to the host, the numpy plant, x back;
+  (b) episode: BatchHandle.run_episode: `steps` steps enqueued on the handle's stream, the point-mass model as the plant on the device,
+               one synchronisation and one copy of the trajectory at the end;
+  (c) floor:   `steps` back-to-back mppi_batch_next_device calls on one x, no plant, one synchronisation: what the controller alone costs.
+Each figure is a host clock around `steps` steps; the three alternate, `reps` times, and the median is printed in us per batched step.
+Grids: the default grid of examples/sweep.py (5 x 4 x 5 x 3 = 300 members, its config and task files) and B = 1 (its first point).
+    tools/time_episode.py [--steps N] [--reps R] [--samples K] [--only host|episode|floor] [--dry-run]"""
+import argparse
+import itertools
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import yaml  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+GRID = dict(lams=[0.05, 0.07, 0.1, 0.15, 0.2], upsilons=[1.0, 1.4, 1.8, 2.0], gammas=[0.05, 0.07, 0.1, 0.15, 0.2], noises=[0.10, 0.15, 0.20])
+
+
+def sweep_kw(samples, B):
+    """BatchHandle's keywords of the first B points of the sweep's default grid (examples/sweep.py main) -> (keywords, dt, mass)"""
+    with open(os.path.join(ROOT, "examples", "config", "point_mass3d.yaml")) as fh:
+        conf = yaml.safe_load(fh)
+    with open(os.path.join(ROOT, "examples", "config", "static_task3d.yaml")) as fh:
+        task = yaml.safe_load(fh)
+    s, a, dt, mass = conf["state-dim"], conf["action-dim"], float(conf["dt"]), float(conf["mass"])
+    grid = list(itertools.product(GRID["lams"], GRID["upsilons"], GRID["gammas"], GRID["noises"]))[:B]
+    n = len(grid)
+    return dict(n=n, k=samples or conf["samples"], tau=conf["horizon"], s_dim=s, a_dim=a, dt=dt, mass=mass, goal=np.asarray(task["goal"], np.float32),
+                Q=np.asarray(task["Q"], np.float32), action_cost=1, upsilon_scales_noise=True, seeds=[1] * n, lams=[g[0] for g in grid],
+                upsilons=[g[1] for g in grid], gammas=[g[2] for g in grid], sigmas=[g[3] * np.eye(a, dtype=np.float32) for g in grid]), dt, mass
+
+
+def time_grid(m, B, samples, steps, reps, only=None):
+    import torch
+    from sweep import plant
+    kw, dt, mass = sweep_kw(samples, B)
+    n, s, a = kw["n"], kw["s_dim"], kw["a_dim"]
+    hs = {k: m.BatchHandle(**kw) for k in ("host", "episode", "floor") if only in (None, k)}  # a handle each: the three never share a sequence
+    xd, ud = torch.zeros((n, s), device="cuda"), torch.zeros((n, a), device="cuda")
+    torch.cuda.synchronize()
+
+    def host(h, k):
+        X = np.zeros((n, s), np.float32)
+        for _ in range(k):
+            X = plant(X, h.next(X), dt, mass)
+
+    def episode(h, k):
+        h.run_episode(np.zeros((n, s), np.float32), k)
+
+    def floor(h, k):
+        for _ in range(k):
+            h.next_device(xd.data_ptr(), ud.data_ptr(), None)
+        h.synchronize()
+    runs = {k: (f, hs[k]) for k, f in (("host", host), ("episode", episode), ("floor", floor)) if k in hs}
+    for f, h in runs.values():  # warm-up: code objects loaded, LDS ceilings raised, the staging allocated, clocks up
+        f(h, max(10, steps // 4))
+        f(h, steps)
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, (f, h) in runs.items():
+            t0 = time.perf_counter()
+            f(h, steps)
+            t[k].append((time.perf_counter() - t0) / steps)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    for k, w in med.items():
+        print("B=%-3d K=%-5d H=%-3d a=%d  %-7s %9.2f us per batched step  (spread over %d reps: %.2f-%.2f us)" % (
+            n, kw["k"], kw["tau"], a, k, w * 1e6, reps, min(t[k]) * 1e6, max(t[k]) * 1e6), flush=True)
+    if len(med) == 3:
+        print("B=%-3d K=%-5d H=%-3d a=%d  episode / host = %.3f   episode - floor = %.2f us per step" % (
+            n, kw["k"], kw["tau"], a, med["episode"] / med["host"], (med["episode"] - med["floor"]) * 1e6), flush=True)
+    for h in hs.values():
+        h.close()
+    return med
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=300, help="steps per timed loop (the sweep's default: 300)")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--samples", type=int, default=None, help="samples per member (default: the sweep config's)")
+    ap.add_argument("--only", choices=("host", "episode", "floor"), help="time one of the three alone")
+    ap.add_argument("--dry-run", action="store_true", help="print the grids and build their keywords, time nothing (no GPU)")
+    o = ap.parse_args()
+    grids = (300, 1)
+    if o.dry_run:
+        for B in grids:
+            kw, dt, mass = sweep_kw(o.samples, B)
+            print("B=%-3d K=%-5d H=%-3d a=%d  dt %g mass %g  %s" % (kw["n"], kw["k"], kw["tau"], kw["a_dim"], dt, mass, sorted(kw)), flush=True)
+        return
+    import torch
+    import mppi_tf_amd as m
+    print("tools/time_episode.py: %s, steps %d, reps %d" % (torch.cuda.get_device_name(0), o.steps, o.reps), flush=True)
+    for B in grids:
+        time_grid(m, B, o.samples, o.steps, o.reps, o.only)
+
+
+if __name__ == "__main__":
+    main()

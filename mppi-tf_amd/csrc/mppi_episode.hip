@@ -1,4 +1,4 @@
-// mppi_episode.hip — the plant of a closed-loop episode (mppi_run_episode / mppi_batch_run_episode, mppi_capi.hip): the one launch that
+// mppi_episode.hip — the plant of a closed-loop episode (mppi_run_episode / mppi_batch_run_episode, mppi_capi_step.hip): the one launch that
 // follows a control step and closes the loop on the device. One LANE per member of the handle (a lone handle: one lane). For member m it
 //   reads  x_t, the step's u_t, the disturbance w_t and the goal of step t + 1,
 //   writes C[t] = the state cost of x_t under the goal still in force (mppi_state_cost's value),

@@ -1,5 +1,7 @@
 // mppi_handle.hip.h — host-side state of one controller (mppi_handle) and the launchers of the rollout kernels.
-// The library is several translation units compiled in parallel (mppi-tf_amd/build.py): mppi_capi.hip holds the C-ABI,
+// The library is several translation units compiled in parallel (mppi-tf_amd/build.py): the C-ABI is split by concern — mppi_capi.hip
+// (creation), mppi_capi_set.hip (setters, accessors), mppi_capi_step.hip (the control step), mppi_capi_shard.hip, mppi_capi_log.hip,
+// mppi_capi_debug.hip — behind one internal header, mppi_capi.hip.h;
 // mppi_launch_tile.hip / _pc.hip / _mlp.hip / _batch.hip instantiate one kernel family each for ONE action dimension per object
 // (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step, mppi_episode.hip the plant of a closed-loop
 // episode. This header is
@@ -114,7 +116,7 @@ struct mppi_handle {
     // the pre-launched pipelined step (MPPI_TUNE_PRELAUNCH; k_step_pc<.., STEP_PRE>): steps alternate between `stream` and `stream2`
     int prelaunch = 0;            // tuning: mppi_next_device on the handle's own stream pre-launches (0: off)
     hipStream_t stream2 = nullptr;
-    hipEvent_t pre_ev = nullptr, pre_ev2 = nullptr; // start-up order (pre_step, mppi_capi.hip)
+    hipEvent_t pre_ev = nullptr, pre_ev2 = nullptr; // start-up order (pre_step, mppi_capi_step.hip)
     unsigned long long *d_ugr = nullptr; // [2][HA] sequence granules {value, tag}
     int *d_cu_ctr = nullptr;             // [4096] workgroup arrivals per CU (role placement of a pre-launched grid)
     bool pre_active = false;      // steps are in flight on both streams; the plain U buffers / step counter are valid again after pre_quiesce
@@ -232,7 +234,7 @@ struct mppi_step_launch {
 #define MPPI_DECL_A(NAME, R, ...) R mppi_##NAME##_a1(__VA_ARGS__); R mppi_##NAME##_a2(__VA_ARGS__); R mppi_##NAME##_a3(__VA_ARGS__); R mppi_##NAME##_a4(__VA_ARGS__);
 #define MPPI_MEMBER(NAME, R, ...) R (*NAME)(__VA_ARGS__);
 MPPI_UNIT_ENTRIES(MPPI_DECL_A)
-struct mppi_unit_a { MPPI_UNIT_ENTRIES(MPPI_MEMBER) }; // one row per action dimension (mppi_capi.hip holds the table)
+struct mppi_unit_a { MPPI_UNIT_ENTRIES(MPPI_MEMBER) }; // one row per action dimension (mppi_capi_step.hip holds the table)
 #undef MPPI_DECL_A
 #undef MPPI_MEMBER
 // the 13-state AUV family (mppi_launch_gen.hip)

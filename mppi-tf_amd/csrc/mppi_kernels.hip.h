@@ -296,7 +296,7 @@ __global__ __launch_bounds__(64 * (NP + 1), (NSLOT * 4 * A <= 80 ? NP + 1 : 2)) 
 // dependent L2 round trips per thread (measured 76 µs at K=65536); this level runs on
 // ceil(nb/kGroup) CUs with kGroup independent loads in flight per thread instead.
 // neutral records in every slot (see record_slot): launched at create and when a handle changes its record count
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_STEP) // non-template kernel: defined in ONE translation unit (mppi_capi_step.hip)
 __global__ void k_fill_records(float *__restrict__ recs, int nbp, int ncol)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -308,7 +308,7 @@ constexpr int kGroup = 16;
 // Scalars arrive as kernel arguments (SGPRs at wave start) rather than through DevConsts: these
 // kernels are a chain of dependent memory round trips, and every hop removed is ~0.5-1 µs.
 // Input element (b, col) at recs[b*sb + col*sc]; output records are row-major [ng, 2+HA].
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_STEP) // non-template kernel: defined in ONE translation unit (mppi_capi_step.hip)
 __global__ __launch_bounds__(kThreads) void k_combine_group(
     const float *__restrict__ recs, int sb, int sc, int nb, int HA, float neg_inv_lambda, float *__restrict__ out, const float *__restrict__ nil_dev)
 {
@@ -414,7 +414,6 @@ __device__ __forceinline__ void column_combine(Load ld, int nb, float neg_inv_la
     beta_out = beta; eta_out = eta; V_out = V;
 }
 
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
 // Behind a PRE-LAUNCHED rollout (k_step_pc<.., STEP_PRE>, mppi_step.hip.h): the sequence travels between the steps as 8-byte {value, tag}
 // granules — the finish of step n reads U from granules `in` (complete: its rollout waited for every one of them), writes the SHIFTED U' as
 // granules `out` tagged `tag` (what step n+1's rollout, already resident on the other stream, is polling for) beside the plain U_out, and
@@ -426,6 +425,7 @@ struct FinishPre {
     unsigned long long step;
 };
 
+#if defined(MPPI_UNIT_CAPI_STEP) // non-template kernel: defined in ONE translation unit (mppi_capi_step.hip)
 __global__ __launch_bounds__(kThreads) void k_finish_cols(
     const float *__restrict__ recs, int sb, int sc, int nb, int HA, int a, float neg_inv_lambda,
     const float *__restrict__ U_in, float *__restrict__ U_out, float *__restrict__ u_out,
@@ -543,7 +543,7 @@ __device__ __forceinline__ unsigned long long xchg_wait(const unsigned long long
 // no spins, zero update — instead of burning one deadline per queued step; mppi_shard_p2p_step refuses further steps
 // as soon as the host sees the flag (MPPI_ERR_EXCHANGE), and ShardedController re-synchronises U and the step counter
 // from rank 0 before it continues on the all-gather path (distributed.py).
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_STEP) // non-template kernel: defined in ONE translation unit (mppi_capi_step.hip)
 __global__ __launch_bounds__(kThreads) void k_finish_cols_xchg(
     const float *__restrict__ recs, int sb, int sc, int nb, int HA, int a, float neg_inv_lambda,
     const float *__restrict__ U_in, float *__restrict__ U_out, float *__restrict__ u_out,
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(kThreads) void k_finish_cols_xchg(
 // k_savgol: filterSeq (controller_base.py:277-291): out[t,j] = Σ_i rows[t,i]·in[start[t]+i, j]. rows holds, for
 // every t, the `window` Savitzky-Golay weights that evaluate the least-squares polynomial of the window starting at
 // start[t] at position t (centre for interior rows, off-centre for the 'interp' edges); built on the host in fp64.
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_STEP) // non-template kernel: defined in ONE translation unit (mppi_capi_step.hip)
 __global__ void k_savgol(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ rows,
                          const int *__restrict__ start, int H, int a, int window)
 {
@@ -612,7 +612,7 @@ __global__ void k_savgol(const float *__restrict__ in, float *__restrict__ out, 
 // k_xchg_probe: the exchange's self-test, run once after the inboxes are attached and before the first step: the
 // same packets, stores and spins on a separate probe region of the inbox (after the 2*HA*G*3 step slots), with a
 // known payload. got[g] = the value received from rank g (the host checks got[g] == payload(g, seq)).
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_SHARD) // non-template kernel: defined in ONE translation unit (mppi_capi_shard.hip)
 __global__ void k_xchg_probe(XchgPeers peers, size_t probe_off, int G, int rank, unsigned seq, float payload,
                              long long timeout_ticks, unsigned *status, unsigned *status_dev, float *got)
 {
@@ -645,7 +645,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // One sample per thread, plain loops in the reference order (mul and add rounded separately,
 // input index ascending): the slow, exactly-ordered evaluation behind mppi_model_step for MLP handles.
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_DEBUG) // non-template kernel: defined in ONE translation unit (mppi_capi_debug.hip)
 __global__ void k_mlp_step_ref(const DevConsts *__restrict__ C, const MlpDev *__restrict__ M,
                                const float *__restrict__ x, int kx, const float *__restrict__ v, int k,
                                float *__restrict__ scratch, float *__restrict__ out_next)
@@ -941,7 +941,7 @@ __global__ __launch_bounds__(kMlpThreads, 2) void k_rollout_mlp(
 namespace mppi {
 
 // min / max of the costs (Py normalizeCost, controller_base.py:468-474): out[0]=min, out[1]=max-min
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_STEP) // non-template kernel: defined in ONE translation unit (mppi_capi_step.hip)
 // nil_out != NULL: also out[2] = *nil_out = neg_inv_lambda / (max - min) — the soft-min temperature at which the RAW costs weigh
 // as the normalised ones do at lambda (exp(-(c'-min c')/lambda) = exp(-(c-min c)/(lambda (max-min)))): the second rollout pass of
 // the two-pass normalizeCost path reads it from a DevConsts copy, the finish from out[2]
@@ -985,7 +985,7 @@ __global__ void k_range_apply(const float *__restrict__ range, float *__restrict
 #endif
 
 // c' = (c - min)/(max - min)  (norm_arg with normalize=True, controller_base.py:468-474)
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_STEP) // non-template kernel: defined in ONE translation unit (mppi_capi_step.hip)
 __global__ void k_cost_normalize(const float *__restrict__ cost, int K, const float *__restrict__ mm, float *__restrict__ out)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -994,7 +994,7 @@ __global__ void k_cost_normalize(const float *__restrict__ cost, int K, const fl
 #endif
 
 // Per-sample intermediates of the update for inspection (mExpArg, mExp, mWeights :170-186)
-#if defined(MPPI_UNIT_CAPI) // non-template kernel: defined in ONE translation unit (mppi_capi.hip)
+#if defined(MPPI_UNIT_CAPI_DEBUG) // non-template kernel: defined in ONE translation unit (mppi_capi_debug.hip)
 __global__ void k_weights(const DevConsts *__restrict__ C, const float *__restrict__ cost, int K,
                           const float *__restrict__ beta_eta, float *__restrict__ arg_out,
                           float *__restrict__ exp_out, float *__restrict__ w_out, const float *__restrict__ nil_dev)

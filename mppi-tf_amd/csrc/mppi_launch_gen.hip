@@ -1,5 +1,5 @@
 // mppi_launch_gen.hip — the 13-state AUV family (mppi_gen.hip.h): constants, launchers and helper kernels of handles whose
-// model_base is AUVModel / NNAUVModel. One translation unit; mppi_capi.hip reaches it through the functions declared in
+// model_base is AUVModel / NNAUVModel. One translation unit; the C-ABI units (mppi_capi*.hip) reach it through the functions declared in
 // mppi_handle.hip.h (mppi_gen_*), the handle keeps an opaque pointer to GenState.
 #include "mppi_handle.hip.h"
 #include "mppi_gen.hip.h"

@@ -1,5 +1,5 @@
 // mppi_launch_step.hip — instantiates k_step_pc (the whole step in one launch / the armed launch, mppi_step.hip.h) for ONE action
-// dimension (-DMPPI_UNIT_A). Diagonal-Q quadratic cost, the step's one pass: the shapes mppi_capi.hip's step_shape_ok admits.
+// dimension (-DMPPI_UNIT_A). Diagonal-Q quadratic cost, the step's one pass: the shapes step_shape_ok (mppi_capi.hip.h) admits.
 #include "mppi_handle.hip.h"
 #include "mppi_step.hip.h"
 #ifndef MPPI_UNIT_A

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""The reference's experiment as one script: a controller whose model is LEARNED (NNAUVModel, examples/config/auv_nn_model.yaml: Dense(32)
+x 3 + Dense(13), random initial weights) drives the true vehicle (the rexrov2 Fossen model), logs every transition, trains on them and
+takes the new weights — round after round. A round's control steps run on the device as ONE call, run_episode(..., plant=fossen): the
+controller plans with its network, the state is stepped by the Fossen plant handle, no host round trip between the steps.
+    python examples/learn_loop.py                                             # 4 rounds of 50 steps, K = 1024, H = 20, 100 epochs
+    python examples/learn_loop.py --rounds 2 --samples 128 --horizon 8 --steps 8 --epochs 3 --hidden 16 --layers 1
+Each round: run_episode from x0 -> every (X[t], U[t], X[t+1]) into LearnerBase.add_rb -> statistics, train_all on the whole buffer ->
+the new weights and normalisation into the controller (Handle.set_mlp, the mppi_set_mlp path). Each round prints the mean state cost of
+its episode and the one-step error of the model on that round's transitions, before and after the training. The script makes no claim
+about convergence: it shows the loop, and the numbers say what the rounds did."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mppi_tf_amd as m  # noqa: E402
+from mppi_tf_amd.auv import auv_task  # noqa: E402
+
+
+def glorot(dims, seed):
+    """Keras' default initialisation of Dense layers: glorot-uniform kernels, zero biases"""
+    rng = np.random.default_rng(seed)
+    lim = [np.sqrt(6.0 / (dims[i] + dims[i + 1])) for i in range(len(dims) - 1)]
+    return dict(W=[rng.uniform(-lim[i], lim[i], (dims[i], dims[i + 1])).astype(np.float32) for i in range(len(dims) - 1)],
+                b=[np.zeros(dims[i + 1], np.float32) for i in range(len(dims) - 1)])
+
+
+def one_step_error(model, X, U):
+    """mean squared error of the model's one-step prediction on the transitions (X[t], U[t]) -> X[t+1]"""
+    pred = np.asarray(model.predict(X[:-1, :, None], U[:, :, None]), np.float64)[..., 0]
+    return float(np.mean((pred - X[1:]) ** 2))
+
+
+def run(o):
+    """-> (the learner, the rounds' episodes [(X, U, C)], the rounds' printed figures [(mean cost, error before, error after, loss first,
+    loss last)])"""
+    task = auv_task(o.horizon, learned=True)
+    x0 = np.asarray(task.pop("x0"), np.float32)
+    model = m.NNAUVModel(weights=glorot([16] + [o.hidden] * o.layers + [13], o.seed), dt=task["dt"])
+    cont = m.Handle(k=o.samples, nnauv=model.mlp(), **task)
+    fossen = m.Handle(k=1, tau=1, s_dim=13, a_dim=6, dt=task["dt"], sigma=np.eye(6, dtype=np.float32), goal=np.zeros(13, np.float32),
+                      auv=auv_task(1)["auv"])  # the plant: a handle that runs no rollouts, only its model is used
+    learner = m.LearnerBase(model, bufferSize=o.rounds * o.steps)
+    episodes, figures = [], []
+    for r in range(o.rounds):
+        X, U, Cs = cont.run_episode(x0, o.steps, plant=fossen)
+        episodes.append((X, U, Cs))
+        learner.add_rb(X[:-1, :, None], U[:, :, None], X[1:, :, None])
+        before = one_step_error(model, X, U)
+        learner.stats()
+        first, last = learner.train_all(learningRate=o.lr, epoch=o.epochs)
+        cont.set_mlp(model.mlp())
+        after = one_step_error(model, X, U)
+        figures.append((float(np.mean(Cs)), before, after, first, last))
+        print("round %d: %d steps, mean state cost %.6g, one-step error of the model on this round's transitions %.6g -> %.6g "
+              "(%d transitions, %d epochs, normalised loss %.6g -> %.6g)" % (r + 1, o.steps, figures[-1][0], before, after, learner.rb.n,
+                                                                           o.epochs, first, last), flush=True)
+    cont.close()
+    fossen.close()
+    return learner, episodes, figures
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="a learned controller on the Fossen plant: episode, train, new weights, round after round")
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("-s", "--steps", type=int, default=50, help="control steps per round (one run_episode call)")
+    ap.add_argument("--samples", type=int, default=1024)
+    ap.add_argument("--horizon", type=int, default=20)
+    ap.add_argument("--epochs", type=int, default=100, help="Adam steps per round on the whole replay buffer")
+    ap.add_argument("--lr", type=float, default=3e-3)
+    ap.add_argument("--hidden", type=int, default=32, choices=(16, 32), help="width of the hidden layers")
+    ap.add_argument("--layers", type=int, default=3, choices=(1, 2, 3), help="hidden layers")
+    ap.add_argument("--seed", type=int, default=0, help="of the initial weights")
+    return run(ap.parse_args(argv))
+
+
+if __name__ == "__main__":
+    main()

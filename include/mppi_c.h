@@ -476,6 +476,31 @@ mppi_status mppi_run_episode(mppi_handle *h, const float *x0, int n_x, int n_ste
 mppi_status mppi_batch_run_episode(mppi_handle *h, const float *x0, int n_x, int n_steps, const float *goals, const float *disturbance,
                                    float *X_out, float *U_out, float *C_out);
 
+/* ---- ... against a separate plant: the model of ANOTHER handle steps the state ---------------------------------------------------------
+ * mppi_run_episode / mppi_batch_run_episode in every respect (the goal per step, C[t] under the controller's cost and goal, the ordinary
+ * control step, the raw fp32 add of the disturbance, where the handle ends) but step 4:
+ *   4. x_{t+1} = model_of(plants[m])(x_t, U[t]) for member m (plants[0] when n_plants is 1), bit for bit what mppi_model_step on that
+ *      plant handle returns as out_next.
+ * A plant is an ordinary lone, unsharded handle on the controller's device with the controller's s_dim and a_dim. Only its model is used:
+ * mass and dt of the point mass, the mppi_auv_desc of the Fossen model, the network of a learned model. Its cost, goal, action sequence,
+ * step counter and log are neither read nor written; it may be a handle that runs no rollouts (k = 1, tau = 1), and it may be h itself.
+ * n_plants is 1 (every member shares the plant; the only value for a lone controller) or B (member m steps with plants[m]).
+ * Served: every controller mppi_run_episode / mppi_batch_run_episode serves, with any plant model of its dimensions — a learned
+ * controller on the Fossen plant, a Fossen controller on a learned plant, a point mass on a point mass of another mass or dt, ... Plants
+ * per member (n_plants = B > 1) are served for the analytic models, the point mass and the Fossen model. A learned plant is shared
+ * (n_plants = 1): its model-step kernel takes one launch over the B rows.
+ * Everything is enqueued on the CONTROLLER's stream, with one synchronisation at the end; the launches per step are those of the plain
+ * episode. Each plant's own stream is synchronised once at entry, so that an mppi_set_mlp in flight on a plant is complete before its
+ * weights are read. Plants are only read, and nothing outlives the call.
+ * MPPI_ERR_INVALID_ARG: plants NULL or an entry NULL, n_plants not 1 or B, a batched or a sharded plant, a plant whose s_dim, a_dim or
+ * device differs from the controller's. MPPI_ERR_UNSUPPORTED: learned plants per member, a plant whose model does not step the
+ * controller's state layout. Every refusal of mppi_run_episode / mppi_batch_run_episode applies, the lone entry point on a batched handle
+ * and the reverse included. Nothing is enqueued before a refusal. */
+mppi_status mppi_run_episode_plant(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x, int n_steps,
+                                   const float *goals, const float *disturbance, float *X_out, float *U_out, float *C_out);
+mppi_status mppi_batch_run_episode_plant(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x, int n_steps,
+                                         const float *goals, const float *disturbance, float *X_out, float *U_out, float *C_out);
+
 /* ---- the learner of the learned model_base (replaces LearnerBase.train / _train_step, learners/learner_base.py:324-358,
  * 469-496; train_all :146-153) --------------------------------------------------------------------------------------------
  * Full-batch Adam on the mean squared error of the network's prediction against the (normalised) targets, for the

@@ -136,6 +136,9 @@ SIGNATURES = {
     # closed-loop episodes on the device (Handle.run_episode, BatchHandle.run_episode)
     "mppi_run_episode": (C.c_int, [_H, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
     "mppi_batch_run_episode": (C.c_int, [_H, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
+    # ... against a separate plant: another handle's model (run_episode(..., plant=))
+    "mppi_run_episode_plant": (C.c_int, [_H, C.POINTER(_H), C.c_int, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
+    "mppi_batch_run_episode_plant": (C.c_int, [_H, C.POINTER(_H), C.c_int, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
     # the learner (LearnerBase.train / _train_step)
     "mppi_learner_create": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(FP), C.POINTER(FP), C.c_int, C.POINTER(_H)]),
     "mppi_learner_destroy": (None, [_H]),
@@ -337,13 +340,21 @@ class _HandleBase:
     def synchronize(self):
         self._check(self.lib.mppi_synchronize(self.h))
 
-    def _run_episode(self, name, lead, x0, n_steps, goals, disturbance):
+    def _run_episode(self, name, lead, x0, n_steps, goals, disturbance, plant=None):
         """n_steps closed-loop steps through the entry point `name` (mppi_run_episode / mppi_batch_run_episode); lead = () for a lone handle, (n,) for a batch:
         x0 [*lead, s], goals / disturbance [n_steps, *lead, s] or None -> (X [n_steps+1, *lead, s], U [n_steps, *lead, a], C [n_steps, *lead]).
-        Shapes are checked here, before the library is called: a bad one raises ValueError."""
+        plant: None (the handle's own model, through `name`), a Handle, or for a batch a sequence of n Handles (through `name`_plant).
+        Shapes and the plant count are checked here, before the library is called: a bad one raises ValueError."""
         n_steps = int(n_steps)
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1, not %d" % n_steps)
+        plants = None
+        if plant is not None:
+            plants = [plant] if isinstance(plant, Handle) else (list(plant) if isinstance(plant, (list, tuple)) else None)
+            if plants is None or not all(isinstance(p, Handle) for p in plants):
+                raise ValueError("plant must be a Handle%s" % (" or a sequence of %d Handles" % lead[0] if lead else ""))
+            if len(plants) != 1 and (not lead or len(plants) != lead[0]):
+                raise ValueError("plant must be one Handle%s, not %d" % (" or %d of them" % lead[0] if lead else "", len(plants)))
 
         def shaped(name, v, shape):
             v = np.asarray(v, dtype=np.float32)
@@ -356,7 +367,12 @@ class _HandleBase:
         X = np.zeros((n_steps + 1, *lead, self.s), np.float32)
         U = np.zeros((n_steps, *lead, self.a), np.float32)
         Cs = np.zeros((n_steps, *lead), np.float32)
-        self._check(getattr(self.lib, name)(self.h, fp(x0), x0.size, n_steps, fp(goals), fp(disturbance), fp(X), fp(U), fp(Cs)))
+        if plants is None:
+            self._check(getattr(self.lib, name)(self.h, fp(x0), x0.size, n_steps, fp(goals), fp(disturbance), fp(X), fp(U), fp(Cs)))
+            return X, U, Cs
+        ph = (_H * len(plants))(*[p.h for p in plants])
+        self._check(getattr(self.lib, name + "_plant")(self.h, ph, len(plants), fp(x0), x0.size, n_steps, fp(goals), fp(disturbance), fp(X), fp(U),
+                                                       fp(Cs)))
         return X, U, Cs
 
     def rollout_kernel_name(self):
@@ -469,12 +485,14 @@ class Handle(_HandleBase):
         self._check(self.lib.mppi_next_with_noise(self.h, fp(x), x.size, fp(eps), eps.size, fp(u), u.size))
         return u
 
-    def run_episode(self, x0, n_steps, goals=None, disturbance=None):
+    def run_episode(self, x0, n_steps, goals=None, disturbance=None, *, plant=None):
         """mppi_run_episode: n_steps control steps on the device with the handle's own model as the plant, no host round trip between them.
         x0 [s]; goals [n_steps, s]: the goal in force at step t; disturbance [n_steps, s]: w_t added to the plant's x'
         -> (X [n_steps+1, s] the realised trajectory, U [n_steps, a] the controls, C [n_steps] the state cost of x_t under step t's goal).
-        The handle ends where the host loop set_goal, next, model_next leaves it."""
-        return self._run_episode("mppi_run_episode", (), x0, n_steps, goals, disturbance)
+        The handle ends where the host loop set_goal, next, model_next leaves it.
+        plant: another Handle (lone, unsharded, same device, s_dim and a_dim) whose model steps the state instead (mppi_run_episode_plant):
+        x' is plant.model_next(x, u); nothing else of the plant is read, and nothing of it is written."""
+        return self._run_episode("mppi_run_episode", (), x0, n_steps, goals, disturbance, plant)
 
     def save_next(self, x_next):
         x = f32(x_next).ravel()
@@ -716,10 +734,12 @@ class BatchHandle(_HandleBase):
         """x_ptr [n, s_dim] -> u_ptr [n, a_dim], device pointers; enqueue only (stream: Handle.next_device's convention)"""
         self._check(self.lib.mppi_batch_next_device(self.h, x_ptr, u_ptr, self._stream(stream)))
 
-    def run_episode(self, X0, n_steps, goals=None, disturbance=None):
+    def run_episode(self, X0, n_steps, goals=None, disturbance=None, *, plant=None):
         """mppi_batch_run_episode: Handle.run_episode for every member at once. X0 [n, s]; goals / disturbance [n_steps, n, s]
-        -> (X [n_steps+1, n, s], U [n_steps, n, a], C [n_steps, n]); member m's slices are its lone handle's episode."""
-        return self._run_episode("mppi_batch_run_episode", (self.n,), X0, n_steps, goals, disturbance)
+        -> (X [n_steps+1, n, s], U [n_steps, n, a], C [n_steps, n]); member m's slices are its lone handle's episode.
+        plant: a Handle every member's state is stepped with, or a sequence of n Handles, member m's at [m] (mppi_batch_run_episode_plant;
+        a learned plant is shared: a sequence of n > 1 learned plants is refused)."""
+        return self._run_episode("mppi_batch_run_episode", (self.n,), X0, n_steps, goals, disturbance, plant)
 
     def get_action_sequences(self):
         U = np.zeros((self.n, self.tau, self.a), np.float32)

@@ -13,6 +13,7 @@
 
 #define MPPI_UNIT_CAPI_STEP 1
 #include "mppi_capi.hip.h"
+#include "mppi_episode_plant.hip.h"
 
 namespace mppi_capi {
 
@@ -595,9 +596,68 @@ static mppi_status ensure_episode_staging(mppi_handle *h, size_t floats)
     return MPPI_OK;
 }
 
+static bool learned_model(const mppi_handle *h)
+{
+    const int mk = h->hc.model_kind;
+    return mk == MPPI_MODEL_MLP || mk == MPPI_MODEL_NN_AUV || mk == MPPI_MODEL_NN_AUV_SPEED;
+}
+
+// ---- ... against a separate plant (mppi_run_episode_plant / mppi_batch_run_episode_plant): step 4 runs the model of ANOTHER handle, a
+// lone unsharded one on the controller's device with its s_dim and a_dim. Only the plant's model is read: an analytic one (the point mass,
+// the Fossen model) through its constants block on the device, whose address goes into a table of B pointers in the episode staging
+// (member m's plant at [m]; a shared plant repeats one pointer; written once per call) that the plant variant of the episode kernel
+// reads (mppi_episode_plant.hip); a learned one through its own model-step kernel, ONE launch over the B rows on the controller's
+// stream, closed by the plain episode kernel — which is why a learned plant is shared by all members. The launches per step are the
+// plain episode's.
+struct EpisodePlant {
+    mppi_handle *learned = nullptr;  // the shared learned plant, or none
+    std::vector<const void *> table; // else: the B constants pointers (empty: the controller's own model, the plain episode)
+};
+
+// every refusal of a plant list, before anything is enqueued; fills `out`
+static mppi_status check_plants(mppi_handle *h, const std::string &who, mppi_handle *const *plants, int n_plants, EpisodePlant *out)
+{
+    const int B = members(h);
+    if (!plants) return fail(h, MPPI_ERR_INVALID_ARG, who + "plants is NULL");
+    if (n_plants != 1 && n_plants != B) return fail(h, MPPI_ERR_INVALID_ARG, who + (h->batch ? "n_plants must be 1 or the member count"
+        : "n_plants must be 1 for a lone controller"));
+    for (int i = 0; i < n_plants; ++i) {
+        const mppi_handle *p = plants[i];
+        const std::string which = who + "plant " + std::to_string(i);
+        if (!p) return fail(h, MPPI_ERR_INVALID_ARG, which + " is NULL");
+        if (p->batch) return fail(h, MPPI_ERR_INVALID_ARG, which + " is a batched handle: a plant is a lone handle");
+        if (p->shard_count != 1) return fail(h, MPPI_ERR_INVALID_ARG, which + " is a sharded handle: a plant is an unsharded handle");
+        if (p->s != h->s || p->a != h->a) return fail(h, MPPI_ERR_INVALID_ARG, which + ": its s_dim and a_dim differ from the controller's");
+        if (p->device != h->device) return fail(h, MPPI_ERR_INVALID_ARG, which + " lives on another device than the controller");
+    }
+    if (h->gen ? (h->s != 13 || h->a != 6) : (h->s != 2 * h->a || h->a < 1 || h->a > 4))
+        return fail(h, MPPI_ERR_UNSUPPORTED, who + "the episode kernels serve the point-mass layout (s_dim = 2 a_dim, a_dim <= 4) and the "
+            "13-state family");
+    for (int i = 0; i < n_plants; ++i) {
+        const mppi_handle *p = plants[i];
+        if (learned_model(p)) {
+            if (n_plants > 1) return fail(h, MPPI_ERR_UNSUPPORTED, who + "per-member learned plants: a learned plant is shared by all "
+                "members (n_plants = 1)");
+            if (p->hc.model_kind != MPPI_MODEL_MLP && !h->gen) return fail(h, MPPI_ERR_UNSUPPORTED, who + "a 13-state learned plant "
+                "needs a controller of the 13-state family");
+            out->learned = plants[i];
+            return MPPI_OK;
+        }
+        if ((p->hc.model_kind == MPPI_MODEL_AUV) != (h->gen != nullptr)) return fail(h, MPPI_ERR_UNSUPPORTED, who + "plant " +
+            std::to_string(i) + ": its model does not step the controller's state layout");
+    }
+    out->table.resize(B);
+    for (int m = 0; m < B; ++m) {
+        const mppi_handle *p = plants[n_plants == 1 ? 0 : m];
+        out->table[m] = h->gen ? mppi_gen_dev_consts(p) : static_cast<const void *>(p->dC);
+    }
+    return MPPI_OK;
+}
+
 static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0, int n_x, int n_steps, const float *goals,
                                const float *disturbance,
-                               float *X_out, float *U_out, float *C_out)
+                               float *X_out, float *U_out, float *C_out, mppi_handle *const *plants = nullptr, int n_plants = 0,
+                               bool with_plant = false)
 {
     const int B = members(h), s = h->s, a = h->a;
     const std::string who = std::string(name) + ": ";
@@ -610,12 +670,25 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
         return fail(h, MPPI_ERR_UNSUPPORTED, h->is_gen ? "batched step: the Fossen AUV model runs on k_rollout_auv_pc only"
                                                        : "batched step: the horizon exceeds what this producer count serves (tau <= 132 "
                                                            "with 3 producers)");
+    EpisodePlant plant;
+    if (with_plant)
+        if (mppi_status st = check_plants(h, who, plants, n_plants, &plant); st != MPPI_OK) return st;
     MPPI_ENTER(h);
+    // a plant's stream is drained once, here: an mppi_set_mlp in flight on it is complete before its weights are read (an armed launch of
+    // a plant is retired as any entry point of that handle retires it). Plants are only read from here on.
+    for (int i = 0; with_plant && i < n_plants; ++i) {
+        mppi_handle *p = plants[i];
+        if (p == h || (i > 0 && p == plants[i - 1])) continue;
+        HIP_TRY(h, quiesce(p));
+        HIP_TRY(h, hipStreamSynchronize(p->stream));
+    }
     const size_t n = (size_t)n_steps, xs = (size_t)B * s, us = (size_t)B * a;
-    const size_t kScratch = 2 * kHid; // k_mlp_step_ref: 2 * 256 floats per sample; k_nnauv_step_ref: 128
+    // k_mlp_step_ref: 2 * 256 floats per sample; k_nnauv_step_ref: 128. The handle's own model steps one sample, a learned plant B.
+    const size_t kScratch = 2 * kHid * (plant.learned ? (size_t)B : 1);
     const size_t oX = 0, oU = oX + (n + 1) * xs, oC = oU + n * us, oG = oC + n * B, oW = oG + (goals ? n * xs : 0), oS = oW +
         (disturbance ? n * xs : 0);
-    if (mppi_status st = ensure_episode_staging(h, oS + kScratch); st != MPPI_OK) return st;
+    const size_t oP = (oS + kScratch + 1) & ~(size_t)1; // the plant table: B pointers, 8-byte aligned
+    if (mppi_status st = ensure_episode_staging(h, plant.table.empty() ? oS + kScratch : oP + 2 * (size_t)B); st != MPPI_OK) return st;
     float *dX = h->d_ep + oX, *dU = h->d_ep + oU, *dC = h->d_ep + oC, *dG = goals ? h->d_ep + oG : nullptr, *dW = disturbance
         ? h->d_ep + oW : nullptr;
     float *scratch = h->d_ep + oS;
@@ -629,8 +702,14 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
         HIP_TRY(h, hipMemcpy2DAsync((char *)h->dC + offsetof(DevConsts, goal), sizeof(DevConsts), dG, row, row, B,
             hipMemcpyDeviceToDevice, st));
     }
-    const int mk = h->hc.model_kind;
-    const bool learned = mk == MPPI_MODEL_MLP || mk == MPPI_MODEL_NN_AUV || mk == MPPI_MODEL_NN_AUV_SPEED;
+    static_assert(sizeof(void *) == 2 * sizeof(float), "the plant table takes two floats of staging per pointer");
+    const void *const *dP = plant.table.empty() ? nullptr : reinterpret_cast<const void *const *>(h->d_ep + oP);
+    if (dP) HIP_TRY(h, hipMemcpyAsync(h->d_ep + oP, plant.table.data(), sizeof(void *) * (size_t)B, hipMemcpyHostToDevice, st));
+    // whose model steps the state: a learned plant's kernel over the B rows, else the handle's own learned model on its one row, else
+    // the episode kernel itself (the handle's analytic model, or the plants' through dP)
+    mppi_handle *stepper = plant.learned ? plant.learned : (!with_plant && learned_model(h)) ? h : nullptr;
+    const bool learned = stepper != nullptr;
+    const int mk = learned ? stepper->hc.model_kind : h->hc.model_kind;
     for (int t = 0; t < n_steps; ++t) {
         const float *x_t = dX + (size_t)t * xs;
         float *u_t = dU + (size_t)t * us, *x_next = dX + (size_t)(t + 1) * xs;
@@ -641,14 +720,14 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
             if (mppi_status s_ = plain_step(h, st, SRC_PHILOX, x_t, nullptr, u_t); s_ != MPPI_OK) return s_;
         }
         TraceRange plant_range(h, "mppi:plant");
-        if (mk == MPPI_MODEL_MLP) {
-            mlp_step_ref(h, st, x_t, 1, u_t, 1, scratch, x_next);
+        if (learned && mk == MPPI_MODEL_MLP) {
+            mlp_step_ref(stepper, st, x_t, B, u_t, B, scratch, x_next);
             HIP_TRY(h, hipGetLastError());
-        } else if (learned) HIP_TRY(h, mppi_gen_model_step(h, st, x_t, 1, u_t, 1, scratch, x_next));
+        } else if (learned) HIP_TRY(h, mppi_gen_model_step(stepper, st, x_t, B, u_t, B, scratch, x_next));
         const mppi_episode_tail e{x_t, u_t, dW ? dW + (size_t)t * xs : nullptr, (dG && t + 1 < n_steps) ? dG +
                                   (size_t)(t + 1) * xs : nullptr,
                                   dC + (size_t)t * B, x_next, learned ? 0 : 1};
-        HIP_TRY(h, mppi_launch_episode_tail(h, st, e));
+        HIP_TRY(h, dP ? mppi_launch_episode_tail_plant(h, st, dP, e) : mppi_launch_episode_tail(h, st, e));
     }
     if (X_out) HIP_TRY(h, hipMemcpyAsync(X_out, dX, sizeof(float) * (n + 1) * xs, hipMemcpyDeviceToHost, st));
     if (U_out) HIP_TRY(h, hipMemcpyAsync(U_out, dU, sizeof(float) * n * us, hipMemcpyDeviceToHost, st));
@@ -673,4 +752,21 @@ extern "C" mppi_status mppi_batch_run_episode(mppi_handle *h, const float *x0, i
 {
     MPPI_BATCH_ONLY(h);
     return run_episode(h, "mppi_batch_run_episode", x0, n_x, n_steps, goals, disturbance, X_out, U_out, C_out);
+}
+
+extern "C" mppi_status mppi_run_episode_plant(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x, int n_steps,
+                                              const float *goals, const float *disturbance, float *X_out, float *U_out, float *C_out)
+{
+    if (!h) return MPPI_ERR_INVALID_ARG;
+    if (h->batch) return fail(h, MPPI_ERR_UNSUPPORTED,
+        "mppi_run_episode_plant: a batched handle runs its episodes through mppi_batch_run_episode_plant");
+    return run_episode(h, "mppi_run_episode_plant", x0, n_x, n_steps, goals, disturbance, X_out, U_out, C_out, plants, n_plants, true);
+}
+
+extern "C" mppi_status mppi_batch_run_episode_plant(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x,
+                                                    int n_steps, const float *goals, const float *disturbance, float *X_out, float *U_out,
+                                                    float *C_out)
+{
+    MPPI_BATCH_ONLY(h);
+    return run_episode(h, "mppi_batch_run_episode_plant", x0, n_x, n_steps, goals, disturbance, X_out, U_out, C_out, plants, n_plants, true);
 }

@@ -4,7 +4,7 @@
 // mppi_capi_debug.hip — behind one internal header, mppi_capi.hip.h;
 // mppi_launch_tile.hip / _pc.hip / _mlp.hip / _batch.hip instantiate one kernel family each for ONE action dimension per object
 // (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step, mppi_episode.hip the plant of a closed-loop
-// episode. This header is
+// episode, mppi_episode_plant.hip the same with another handle's model as the plant. This header is
 // what they share.
 #pragma once
 #include "mppi_kernels.hip.h"
@@ -133,8 +133,8 @@ struct mppi_handle {
     // the two batched launches (mppi_launch_batch.hip; the Fossen AUV model: mppi_launch_batch_gen.hip).
     int batch = 0;
     float *d_bx = nullptr, *d_bu = nullptr;
-    // a closed-loop episode's staging (mppi_run_episode / mppi_batch_run_episode): X | U | C | goals | disturbance | model-step scratch, one
-    // allocation that grows on demand
+    // a closed-loop episode's staging (mppi_run_episode / mppi_batch_run_episode): X | U | C | goals | disturbance | model-step scratch
+    // [| the plants' constants pointers: mppi_run_episode_plant], one allocation that grows on demand
     float *d_ep = nullptr;
     size_t ep_cap = 0; // floats
     size_t xchg_step_slots() const { return (size_t)2 * HA * shard_count * 3; }

@@ -3,9 +3,11 @@
   (b) episode: BatchHandle.run_episode: `steps` steps enqueued on the handle's stream, the point-mass model as the plant on the device,
                one synchronisation and one copy of the trajectory at the end;
   (c) floor:   `steps` back-to-back mppi_batch_next_device calls on one x, no plant, one synchronisation: what the controller alone costs.
+With --plant the episode of (b) steps the state with SEPARATE plant handles (run_episode(..., plant=)), twins of the controller's model so
+that the work is the same: `shared` one plant handle for every member, `members` a plant handle per member (a table of B distinct pointers).
 Each figure is a host clock around `steps` steps; the three alternate, `reps` times, and the median is printed in us per batched step.
 Grids: the default grid of examples/sweep.py (5 x 4 x 5 x 3 = 300 members, its config and task files) and B = 1 (its first point).
-    tools/time_episode.py [--steps N] [--reps R] [--samples K] [--only host|episode|floor] [--dry-run]"""
+    tools/time_episode.py [--steps N] [--reps R] [--samples K] [--only host|episode|floor] [--plant shared|members] [--dry-run]"""
 import argparse
 import itertools
 import os
@@ -35,11 +37,15 @@ def sweep_kw(samples, B):
                 upsilons=[g[1] for g in grid], gammas=[g[2] for g in grid], sigmas=[g[3] * np.eye(a, dtype=np.float32) for g in grid]), dt, mass
 
 
-def time_grid(m, B, samples, steps, reps, only=None):
+def time_grid(m, B, samples, steps, reps, only=None, plants=None):
     import torch
     from sweep import plant
     kw, dt, mass = sweep_kw(samples, B)
     n, s, a = kw["n"], kw["s_dim"], kw["a_dim"]
+    # the plant handles of --plant: the controller's own point mass again (k = 1, tau = 1: they run no rollouts)
+    ps = [m.Handle(k=1, tau=1, s_dim=s, a_dim=a, dt=dt, mass=mass) for _ in range({None: 0, "shared": 1, "members": n}[plants])]
+    ep_plant = None if plants is None else (ps[0] if plants == "shared" else ps)
+    ep_name = "episode" if plants is None else "episode (plant: %s)" % plants
     hs = {k: m.BatchHandle(**kw) for k in ("host", "episode", "floor") if only in (None, k)}  # a handle each: the three never share a sequence
     xd, ud = torch.zeros((n, s), device="cuda"), torch.zeros((n, a), device="cuda")
     torch.cuda.synchronize()
@@ -50,7 +56,7 @@ def time_grid(m, B, samples, steps, reps, only=None):
             X = plant(X, h.next(X), dt, mass)
 
     def episode(h, k):
-        h.run_episode(np.zeros((n, s), np.float32), k)
+        h.run_episode(np.zeros((n, s), np.float32), k, plant=ep_plant)
 
     def floor(h, k):
         for _ in range(k):
@@ -69,11 +75,11 @@ def time_grid(m, B, samples, steps, reps, only=None):
     med = {k: float(np.median(v)) for k, v in t.items()}
     for k, w in med.items():
         print("B=%-3d K=%-5d H=%-3d a=%d  %-7s %9.2f us per batched step  (spread over %d reps: %.2f-%.2f us)" % (
-            n, kw["k"], kw["tau"], a, k, w * 1e6, reps, min(t[k]) * 1e6, max(t[k]) * 1e6), flush=True)
+            n, kw["k"], kw["tau"], a, ep_name if k == "episode" else k, w * 1e6, reps, min(t[k]) * 1e6, max(t[k]) * 1e6), flush=True)
     if len(med) == 3:
         print("B=%-3d K=%-5d H=%-3d a=%d  episode / host = %.3f   episode - floor = %.2f us per step" % (
             n, kw["k"], kw["tau"], a, med["episode"] / med["host"], (med["episode"] - med["floor"]) * 1e6), flush=True)
-    for h in hs.values():
+    for h in list(hs.values()) + ps:
         h.close()
     return med
 
@@ -84,6 +90,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--samples", type=int, default=None, help="samples per member (default: the sweep config's)")
     ap.add_argument("--only", choices=("host", "episode", "floor"), help="time one of the three alone")
+    ap.add_argument("--plant", choices=("shared", "members"), help="the episode steps the state with separate plant handles, twins of the "
+                                                                   "controller's model: one for all members, or one per member")
     ap.add_argument("--dry-run", action="store_true", help="print the grids and build their keywords, time nothing (no GPU)")
     o = ap.parse_args()
     grids = (300, 1)
@@ -96,7 +104,7 @@ def main():
     import mppi_tf_amd as m
     print("tools/time_episode.py: %s, steps %d, reps %d" % (torch.cuda.get_device_name(0), o.steps, o.reps), flush=True)
     for B in grids:
-        time_grid(m, B, o.samples, o.steps, o.reps, o.only)
+        time_grid(m, B, o.samples, o.steps, o.reps, o.only, o.plant)
 
 
 if __name__ == "__main__":

@@ -7,8 +7,11 @@ controller plans with its network, the state is stepped by the Fossen plant hand
     python examples/learn_loop.py --rounds 2 --samples 128 --horizon 8 --steps 8 --epochs 3 --hidden 16 --layers 1
 Each round: run_episode from x0 -> every (X[t], U[t], X[t+1]) into LearnerBase.add_rb -> statistics, train_all on the whole buffer ->
 the new weights and normalisation into the controller (Handle.set_mlp, the mppi_set_mlp path). Each round prints the mean state cost of
-its episode and the one-step error of the model on that round's transitions, before and after the training. The script makes no claim
-about convergence: it shows the loop, and the numbers say what the rounds did."""
+its episode, the one-step error of the model on that round's transitions and its H-step OPEN-LOOP error — what an MPPI controller needs
+from its model, because its rollouts are H steps long — each before and after the training. The H-step error takes every window
+x0 = X[t], V = U[t:t+H] of the round's episode and rolls it twice, once on the controller's handle (the learned model) and once on the
+Fossen plant handle (the truth), each as ONE model_rollout call over all windows; the figure is the mean distance between the two
+positions at step H. The script makes no claim about convergence: it shows the loop, and the numbers say what the rounds did."""
 import argparse
 import os
 import sys
@@ -34,9 +37,21 @@ def one_step_error(model, X, U):
     return float(np.mean((pred - X[1:]) ** 2))
 
 
+def h_step_error(cont, plant, X, U, H):
+    """mean position error at step H of the controller's model rolled open-loop along the recorded actions, over every window
+    x0 = X[t], V = U[t:t+H] of the episode, against the plant rolled along the same actions: two model_rollout calls. -> (error, windows)"""
+    n = U.shape[0] - H + 1
+    if n < 1:
+        return float("nan"), 0
+    V = np.ascontiguousarray(np.stack([U[t:t + H] for t in range(n)], axis=1))  # [H, n, a]
+    Xm = cont.model_rollout(X[:n], V, costs=False)[0]
+    Xp = plant.model_rollout(X[:n], V, costs=False)[0]
+    return float(np.mean(np.linalg.norm(Xm[-1, :, :3].astype(np.float64) - Xp[-1, :, :3].astype(np.float64), axis=1))), n
+
+
 def run(o):
     """-> (the learner, the rounds' episodes [(X, U, C)], the rounds' printed figures [(mean cost, error before, error after, loss first,
-    loss last)])"""
+    loss last[, H-step error before, H-step error after: when the episode holds a window of H steps])])"""
     task = auv_task(o.horizon, learned=True)
     x0 = np.asarray(task.pop("x0"), np.float32)
     model = m.NNAUVModel(weights=glorot([16] + [o.hidden] * o.layers + [13], o.seed), dt=task["dt"])
@@ -50,14 +65,17 @@ def run(o):
         episodes.append((X, U, Cs))
         learner.add_rb(X[:-1, :, None], U[:, :, None], X[1:, :, None])
         before = one_step_error(model, X, U)
+        h_before, windows = h_step_error(cont, fossen, X, U, o.horizon)
         learner.stats()
         first, last = learner.train_all(learningRate=o.lr, epoch=o.epochs)
         cont.set_mlp(model.mlp())
         after = one_step_error(model, X, U)
-        figures.append((float(np.mean(Cs)), before, after, first, last))
+        h_after, _ = h_step_error(cont, fossen, X, U, o.horizon)
+        figures.append((float(np.mean(Cs)), before, after, first, last) + ((h_before, h_after) if windows else ()))
+        h_text = ("%.6g -> %.6g m (%d windows)" % (h_before, h_after, windows)) if windows else "n/a (the episode is shorter than H)"
         print("round %d: %d steps, mean state cost %.6g, one-step error of the model on this round's transitions %.6g -> %.6g "
-              "(%d transitions, %d epochs, normalised loss %.6g -> %.6g)" % (r + 1, o.steps, figures[-1][0], before, after, learner.rb.n,
-                                                                           o.epochs, first, last), flush=True)
+              "(%d transitions, %d epochs, normalised loss %.6g -> %.6g), H-step open-loop position error (H = %d) %s" % (
+                  r + 1, o.steps, figures[-1][0], before, after, learner.rb.n, o.epochs, first, last, o.horizon, h_text), flush=True)
     cont.close()
     fossen.close()
     return learner, episodes, figures

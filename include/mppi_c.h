@@ -501,6 +501,38 @@ mppi_status mppi_run_episode_plant(mppi_handle *h, mppi_handle *const *plants, i
 mppi_status mppi_batch_run_episode_plant(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x, int n_steps,
                                          const float *goals, const float *disturbance, float *X_out, float *U_out, float *C_out);
 
+/* ---- open-loop rollouts: the handle's model rolled along n GIVEN action sequences, every state and its cost written out ------------------
+ * "Where does this model go if I apply these actions?" in one call with no host wait inside: the nominal plan, the plan of a chosen sample
+ * (V = U + eps[k]), or the H-step open-loop error of a learned model along recorded actions. The step axis comes first and the trajectory
+ * axis after it, as in the episodes' X[n_steps+1, B, s]:
+ *   x0[kx, s] with kx in {1, n} (one start shared by all trajectories, or one each), V[T, n, a] -> X[T+1, n, s], C[T, n].
+ * For trajectory i:
+ *   X[0, i] = x0[kx == 1 ? 0 : i];
+ *   X[t+1, i] = model(X[t, i], V[t, i]) for t = 0 .. T-1, bit for bit what mppi_model_step returns as out_next;
+ *   C[t, i] = the state cost of X[t+1, i] under the handle's current goal, bit for bit mppi_state_cost's value: the state the step
+ *     PRODUCED, which is the post-step state a rollout of the control step charges (the terminal cost the rollouts add once more is
+ *     C[T-1, i] again; no action cost is computed here).
+ * T is any value >= 1, not tied to the handle's tau. The analytic models (the point mass, the Fossen model) run ONE launch: a lane per
+ * trajectory, the step loop inside the kernel. A learned model (MPPI_MODEL_MLP, NN_AUV, NN_AUV_SPEED) runs T launches of the exactly-ordered
+ * reference kernel behind mppi_model_step and one cost launch: its trajectory here is that REFERENCE-ORDERED evaluation, as with
+ * mppi_model_step — the matrix-core rollout kernels of a control step round differently.
+ * Served: every lone handle mppi_model_step serves, handles that run no rollouts (k = 1, tau = 1) included — the point mass and
+ * MPPI_MODEL_MLP with a_dim 1..4 (s_dim = 2 a_dim), the three 13-state models — with every state cost the handle can hold.
+ * Only the model and the cost with its goal are read: the action sequence, the step counter, the goal, the handle's x, its cost and record
+ * buffers and the transition log are neither read nor written, and an mppi_next after the call returns what it would have returned
+ * without it.
+ * MPPI_ERR_UNSUPPORTED: a batched handle (its members share one model: roll it on a lone handle), a point-mass or MLP handle with
+ * a_dim > 4. MPPI_ERR_INVALID_ARG: n < 1, T < 1 (or n * T > 2^30), kx not 1 or n, x0 or V NULL, no output. Nothing is enqueued before a
+ * refusal. */
+/* host pointers; one synchronisation at the end. Either output may be NULL, not both. */
+mppi_status mppi_model_rollout(mppi_handle *h, const float *x0, int kx, const float *V, int n, int T,
+                               float *X_out, float *C_out);
+/* device pointers, enqueue only on `stream` (NULL = the handle's own; the convention of mppi_next_device). X_dev is required (a learned
+ * model steps from row to row of it); C_dev may be NULL: no cost arithmetic. A learned model's per-row scratch belongs to the handle:
+ * a call on another stream than the previous call's first waits for that stream, which must still exist. */
+mppi_status mppi_model_rollout_device(mppi_handle *h, const float *x0_dev, int kx, const float *V_dev, int n, int T,
+                                      float *X_dev, float *C_dev, void *stream);
+
 /* ---- the learner of the learned model_base (replaces LearnerBase.train / _train_step, learners/learner_base.py:324-358,
  * 469-496; train_all :146-153) --------------------------------------------------------------------------------------------
  * Full-batch Adam on the mean squared error of the network's prediction against the (normalised) targets, for the

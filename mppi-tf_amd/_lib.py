@@ -139,6 +139,9 @@ SIGNATURES = {
     # ... against a separate plant: another handle's model (run_episode(..., plant=))
     "mppi_run_episode_plant": (C.c_int, [_H, C.POINTER(_H), C.c_int, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
     "mppi_batch_run_episode_plant": (C.c_int, [_H, C.POINTER(_H), C.c_int, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
+    # open-loop rollouts of the handle's model (Handle.model_rollout, model_rollout_device)
+    "mppi_model_rollout": (C.c_int, [_H, FP, C.c_int, FP, C.c_int, C.c_int, FP, FP]),
+    "mppi_model_rollout_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # the learner (LearnerBase.train / _train_step)
     "mppi_learner_create": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(FP), C.POINTER(FP), C.c_int, C.POINTER(_H)]),
     "mppi_learner_destroy": (None, [_H]),
@@ -590,6 +593,56 @@ class Handle(_HandleBase):
                                          fp(w), fp(wn), fp(Un)))
         return dict(beta=beta[0], arg=arg, exp=e, nabla=nabla[0], w=w, wn=wn, Unew=Un)
 
+    # ---- open-loop rollouts (mppi_model_rollout, include/mppi_c.h) -------------------------------
+    def model_rollout(self, x0, V, costs=True):
+        """The handle's model rolled along given action sequences, in ONE call: V [T, a] -> (X [T+1, s], C [T]); V [T, n, a] ->
+        (X [T+1, n, s], C [T, n]), the step axis first. x0 is [s] (shared by every trajectory) or [n, s]. X[0] = x0, X[t+1] =
+        model_next(X[t], V[t]) and C[t] = state_cost(X[t+1]) under the current goal, bit for bit those helpers' values; T is free of tau.
+        costs=False: no cost arithmetic, C is None. Nothing of the handle changes. A learned model's trajectory is the reference-ordered
+        evaluation model_next gives, not the rounding of a control step's matrix-core rollouts.
+        Shapes are checked here, before the library is called: a bad one raises ValueError."""
+        V = np.asarray(V, dtype=np.float32)
+        x0 = np.asarray(x0, dtype=np.float32)
+        if V.ndim not in (2, 3) or V.shape[-1] != self.a:
+            raise ValueError("V must have shape (T, %d) or (T, n, %d), not %s" % (self.a, self.a, V.shape))
+        lone = V.ndim == 2
+        T, n = V.shape[0], 1 if lone else V.shape[1]
+        if T < 1 or n < 1:
+            raise ValueError("V must hold T >= 1 steps of n >= 1 trajectories, not %s" % (V.shape,))
+        good = [(self.s,), (1, self.s)] + ([] if lone else [(n, self.s)])
+        if x0.shape not in good:
+            raise ValueError("x0 must have shape %s, not %s" % (" or ".join(str(g) for g in good), x0.shape))
+        x0, V = np.ascontiguousarray(x0).reshape(-1, self.s), np.ascontiguousarray(V).reshape(T, n, self.a)
+        X = np.zeros((T + 1, n, self.s), np.float32)
+        Cs = np.zeros((T, n), np.float32) if costs else None
+        self._check(self.lib.mppi_model_rollout(self.h, fp(x0), x0.shape[0], fp(V), n, T, fp(X), fp(Cs)))
+        if lone:
+            return X[:, 0], (Cs[:, 0] if costs else None)
+        return X, Cs
+
+    def model_rollout_device(self, x0_ptr, kx, V_ptr, n, T, X_ptr, C_ptr=0, stream=None):
+        """mppi_model_rollout_device: the same on device pointers (ints: tensor.data_ptr()), enqueue only. x0 [kx, s] with kx in {1, n},
+        V [T, n, a] -> X [T+1, n, s] (required), C [T, n] (0: none). stream: next_device's convention."""
+        self._check(self.lib.mppi_model_rollout_device(self.h, x0_ptr, int(kx), V_ptr, int(n), int(T), X_ptr, C_ptr or None,
+                                                       self._stream(stream)))
+
+    def sample_trajectories(self, x, U_before, ks):
+        """What the controller planned in the LAST step, read out on the host side: the trajectories of the samples `ks` (indices into the
+        handle's k_local samples). x: the state the step ran from; U_before [tau, a]: the sequence the step started from, read with
+        get_action_sequence() BEFORE next(). -> (X [tau+1, m, s], C [tau, m], eps [m, tau, a]) with m = len(ks): the noise rows of those
+        samples, and model_rollout of V = U_before + eps[k] (an fp32 add: the kernels' v = u + e, without action limits).
+        A diagnostic: it regenerates and copies the whole noise array of the step (debug_get(DBG_NOISE)) to take m rows of it."""
+        ks = np.asarray(ks, dtype=np.int64).reshape(-1)
+        if ks.size < 1 or ks.min() < 0 or ks.max() >= self.k_local:
+            raise ValueError("ks must hold sample indices in [0, %d)" % self.k_local)
+        U = np.asarray(U_before, dtype=np.float32)
+        if U.shape != (self.tau, self.a):
+            raise ValueError("U_before must have shape %s, not %s" % ((self.tau, self.a), U.shape))
+        eps = np.ascontiguousarray(self.debug_get(DBG_NOISE)[ks])
+        V = (U[None] + eps).astype(np.float32)
+        X, Cs = self.model_rollout(np.asarray(x, dtype=np.float32).reshape(self.s), np.ascontiguousarray(V.transpose(1, 0, 2)))
+        return X, Cs, eps
+
     # ---- device-resident step (pointers are ints: tensor.data_ptr()) -----
     def next_device(self, x_ptr, u_ptr, stream=None):
         self._check(self.lib.mppi_next_device(self.h, x_ptr, u_ptr, self._stream(stream)))
@@ -740,6 +793,11 @@ class BatchHandle(_HandleBase):
         plant: a Handle every member's state is stepped with, or a sequence of n Handles, member m's at [m] (mppi_batch_run_episode_plant;
         a learned plant is shared: a sequence of n > 1 learned plants is refused)."""
         return self._run_episode("mppi_batch_run_episode", (self.n,), X0, n_steps, goals, disturbance, plant)
+
+    def model_rollout(self, *args, **kwargs):
+        """refused: the members of a batch share one model, so an open-loop rollout is a lone handle's business (Handle.model_rollout)"""
+        raise MppiError(ERR_UNSUPPORTED, "BatchHandle.model_rollout: the members of a batch share one model; roll it on a lone Handle of "
+                                         "the same model and cost (Handle.model_rollout)")
 
     def get_action_sequences(self):
         U = np.zeros((self.n, self.tau, self.a), np.float32)

@@ -334,6 +334,30 @@ class ControllerBase:
         cost += float(np.asarray(self._cost.state_cost("predict", state)).reshape(-1)[0])  # build_final_step_cost_graph
         return np.asarray(traj), cost
 
+    def predict_trajectories(self, x, actionSeqs=None):
+        """predict_trajectory for n action sequences in ONE device call (Handle.model_rollout on the controller's own handle: its model,
+        its cost and goal; nothing of the controller changes). actionSeqs: None (the nominal sequence) or one sequence [tau, aDim]
+        -> (trajectory [tau, sDim], cost); n sequences [n, tau, aDim] -> (trajectories [tau, n, sDim], costs [n]). The cost convention is
+        predict_trajectory's: the state cost of every state the model passes, added in step order, and the terminal cost once more."""
+        if actionSeqs is None:
+            U = self._h.get_action_sequence()
+        else:
+            U = np.asarray(actionSeqs, np.float32)
+            if U.ndim >= 3 and U.shape[-1] == 1 and U.shape[-2] == self._aDim:  # the reference's column form [.., tau, aDim, 1]
+                U = U[..., 0]
+        if U.shape[-2:] != (self._tau, self._aDim) or U.ndim not in (2, 3):
+            raise ValueError("actionSeqs must have shape (%d, %d) or (n, %d, %d), not %s" % (self._tau, self._aDim, self._tau, self._aDim, U.shape))
+        lone = U.ndim == 2
+        V = U[:, None, :] if lone else U.transpose(1, 0, 2)
+        X, Cs = self._h.model_rollout(np.asarray(x, np.float32).reshape(self._sDim), V)
+        costs = []
+        for i in range(V.shape[1]):
+            c = 0.0
+            for t in range(self._tau):
+                c += float(Cs[t, i])
+            costs.append(c + float(Cs[-1, i]))  # build_final_step_cost_graph
+        return (X[1:, 0], costs[0]) if lone else (X[1:], np.asarray(costs))
+
     def update_model(self):
         """Push the model object's current weights and normalisation into the controller (mppi_set_mlp): what happens implicitly in
         the reference, where learner and controller share the model's tf.Variables (learner_base.py:469-496). Learned models only."""

@@ -129,7 +129,7 @@ extern "C" void mppi_destroy(mppi_handle *h)
                      h->d_record, h->d_dbg, h->d_mm, h->d_eps, h->d_recs, h->d_range, h->d_tile_mm};
     for (float *p : bufs) if (p) (void)hipFree(p);
     if (h->d_step) (void)hipFree(h->d_step);
-    for (float *p : {h->d_bx, h->d_bu, h->d_ep}) if (p) (void)hipFree(p);
+    for (float *p : {h->d_bx, h->d_bu, h->d_ep, h->d_mr}) if (p) (void)hipFree(p);
     if (h->dM) (void)hipFree(h->dM);
     if (h->d_mlp_w) (void)hipFree(h->d_mlp_w);
     if (h->dC) (void)hipFree(h->dC);

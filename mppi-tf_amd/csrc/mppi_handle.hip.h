@@ -4,8 +4,8 @@
 // mppi_capi_debug.hip — behind one internal header, mppi_capi.hip.h;
 // mppi_launch_tile.hip / _pc.hip / _mlp.hip / _batch.hip instantiate one kernel family each for ONE action dimension per object
 // (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step, mppi_episode.hip the plant of a closed-loop
-// episode, mppi_episode_plant.hip the same with another handle's model as the plant. This header is
-// what they share.
+// episode, mppi_episode_plant.hip the same with another handle's model as the plant, mppi_model_rollout.hip the open-loop rollout of the
+// handle's model (kernels and entry points). This header is what they share.
 #pragma once
 #include "mppi_kernels.hip.h"
 #include <hip/hip_ext.h>
@@ -137,6 +137,11 @@ struct mppi_handle {
     // [| the plants' constants pointers: mppi_run_episode_plant], one allocation that grows on demand
     float *d_ep = nullptr;
     size_t ep_cap = 0; // floats
+    // mppi_model_rollout of a learned model (mppi_model_rollout.hip): the per-row scratch of its reference step kernel, grown on demand,
+    // and the stream the last such call was enqueued on
+    float *d_mr = nullptr;
+    size_t mr_cap = 0; // floats
+    hipStream_t mr_stream = nullptr;
     size_t xchg_step_slots() const { return (size_t)2 * HA * shard_count * 3; }
     size_t xchg_inbox_bytes() const { return sizeof(unsigned long long) * (xchg_step_slots() + (size_t)2 * shard_count); }
 };

@@ -11,7 +11,11 @@ its episode, the one-step error of the model on that round's transitions and its
 from its model, because its rollouts are H steps long — each before and after the training. The H-step error takes every window
 x0 = X[t], V = U[t:t+H] of the round's episode and rolls it twice, once on the controller's handle (the learned model) and once on the
 Fossen plant handle (the truth), each as ONE model_rollout call over all windows; the figure is the mean distance between the two
-positions at step H. The script makes no claim about convergence: it shows the loop, and the numbers say what the rounds did."""
+positions at step H. The script makes no claim about convergence: it shows the loop, and the numbers say what the rounds did.
+    python examples/learn_loop.py --model point_mass --hidden 256
+is the same loop for the point mass: the controller's model is NNPointMassModel (MPPI_MODEL_MLP; --hidden 256: Dense(256) x 2, the network
+of the matrix-core rollout kernel, trained by the wide learner), the plant a k = 1, tau = 1 handle of the analytic point mass (2 actions,
+state (x, vx, y, vy)); the H-step error takes the position components 0 and 2."""
 import argparse
 import os
 import sys
@@ -37,7 +41,7 @@ def one_step_error(model, X, U):
     return float(np.mean((pred - X[1:]) ** 2))
 
 
-def h_step_error(cont, plant, X, U, H):
+def h_step_error(cont, plant, X, U, H, pos=(0, 1, 2)):
     """mean position error at step H of the controller's model rolled open-loop along the recorded actions, over every window
     x0 = X[t], V = U[t:t+H] of the episode, against the plant rolled along the same actions: two model_rollout calls. -> (error, windows)"""
     n = U.shape[0] - H + 1
@@ -46,18 +50,31 @@ def h_step_error(cont, plant, X, U, H):
     V = np.ascontiguousarray(np.stack([U[t:t + H] for t in range(n)], axis=1))  # [H, n, a]
     Xm = cont.model_rollout(X[:n], V, costs=False)[0]
     Xp = plant.model_rollout(X[:n], V, costs=False)[0]
-    return float(np.mean(np.linalg.norm(Xm[-1, :, :3].astype(np.float64) - Xp[-1, :, :3].astype(np.float64), axis=1))), n
+    pos = list(pos)
+    return float(np.mean(np.linalg.norm(Xm[-1][:, pos].astype(np.float64) - Xp[-1][:, pos].astype(np.float64), axis=1))), n
 
 
 def run(o):
     """-> (the learner, the rounds' episodes [(X, U, C)], the rounds' printed figures [(mean cost, error before, error after, loss first,
     loss last[, H-step error before, H-step error after: when the episode holds a window of H steps])])"""
-    task = auv_task(o.horizon, learned=True)
-    x0 = np.asarray(task.pop("x0"), np.float32)
-    model = m.NNAUVModel(weights=glorot([16] + [o.hidden] * o.layers + [13], o.seed), dt=task["dt"])
-    cont = m.Handle(k=o.samples, nnauv=model.mlp(), **task)
-    fossen = m.Handle(k=1, tau=1, s_dim=13, a_dim=6, dt=task["dt"], sigma=np.eye(6, dtype=np.float32), goal=np.zeros(13, np.float32),
-                      auv=auv_task(1)["auv"])  # the plant: a handle that runs no rollouts, only its model is used
+    if o.model == "point_mass":
+        # 2 actions, state (x, vx, y, vy): from rest at the origin to (1, -1); the plant is the analytic point mass
+        a, dt, pos = 2, 0.1, (0, 2)
+        task = dict(tau=o.horizon, s_dim=2 * a, a_dim=a, dt=dt, lam=1.0, sigma=np.eye(a, dtype=np.float32), goal=[1.0, 0.0, -1.0, 0.0],
+                    Q=np.array([10.0, 1.0, 10.0, 1.0], np.float32), seed=1)
+        x0 = np.zeros(2 * a, np.float32)
+        hidden = (256, 256) if o.hidden == 256 else (o.hidden,) * o.layers
+        model = m.NNPointMassModel(stateDim=2 * a, actionDim=a, hidden=hidden, weights=glorot([3 * a, *hidden, 2 * a], o.seed), dt=dt)
+        cont = m.Handle(k=o.samples, mlp=model.mlp(), **task)
+        fossen = m.Handle(k=1, tau=1, s_dim=2 * a, a_dim=a, dt=dt, mass=1.0)  # the plant: only its model is used
+    else:
+        pos = (0, 1, 2)
+        task = auv_task(o.horizon, learned=True)
+        x0 = np.asarray(task.pop("x0"), np.float32)
+        model = m.NNAUVModel(weights=glorot([16] + [o.hidden] * o.layers + [13], o.seed), dt=task["dt"])
+        cont = m.Handle(k=o.samples, nnauv=model.mlp(), **task)
+        fossen = m.Handle(k=1, tau=1, s_dim=13, a_dim=6, dt=task["dt"], sigma=np.eye(6, dtype=np.float32), goal=np.zeros(13, np.float32),
+                          auv=auv_task(1)["auv"])  # the plant: a handle that runs no rollouts, only its model is used
     learner = m.LearnerBase(model, bufferSize=o.rounds * o.steps)
     episodes, figures = [], []
     for r in range(o.rounds):
@@ -65,34 +82,42 @@ def run(o):
         episodes.append((X, U, Cs))
         learner.add_rb(X[:-1, :, None], U[:, :, None], X[1:, :, None])
         before = one_step_error(model, X, U)
-        h_before, windows = h_step_error(cont, fossen, X, U, o.horizon)
+        h_before, windows = h_step_error(cont, fossen, X, U, o.horizon, pos)
         learner.stats()
         first, last = learner.train_all(learningRate=o.lr, epoch=o.epochs)
         cont.set_mlp(model.mlp())
         after = one_step_error(model, X, U)
-        h_after, _ = h_step_error(cont, fossen, X, U, o.horizon)
+        h_after, _ = h_step_error(cont, fossen, X, U, o.horizon, pos)
         figures.append((float(np.mean(Cs)), before, after, first, last) + ((h_before, h_after) if windows else ()))
         h_text = ("%.6g -> %.6g m (%d windows)" % (h_before, h_after, windows)) if windows else "n/a (the episode is shorter than H)"
         print("round %d: %d steps, mean state cost %.6g, one-step error of the model on this round's transitions %.6g -> %.6g "
               "(%d transitions, %d epochs, normalised loss %.6g -> %.6g), H-step open-loop position error (H = %d) %s" % (
                   r + 1, o.steps, figures[-1][0], before, after, learner.rb.n, o.epochs, first, last, o.horizon, h_text), flush=True)
+        if getattr(o, "on_round", None) is not None:
+            o.on_round(r, cont, model, X, U)
     cont.close()
     fossen.close()
     return learner, episodes, figures
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description="a learned controller on the Fossen plant: episode, train, new weights, round after round")
+def main(argv=None, on_round=None):
+    """on_round(round, controller handle, model, X, U): called at the end of every round, while the handles are alive"""
+    ap = argparse.ArgumentParser(description="a learned controller on the true plant: episode, train, new weights, round after round")
+    ap.add_argument("--model", default="auv", choices=("auv", "point_mass"), help="auv: NNAUVModel on the Fossen plant; point_mass: NNPointMassModel on the analytic point mass")
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("-s", "--steps", type=int, default=50, help="control steps per round (one run_episode call)")
     ap.add_argument("--samples", type=int, default=1024)
     ap.add_argument("--horizon", type=int, default=20)
     ap.add_argument("--epochs", type=int, default=100, help="Adam steps per round on the whole replay buffer")
     ap.add_argument("--lr", type=float, default=3e-3)
-    ap.add_argument("--hidden", type=int, default=32, choices=(16, 32), help="width of the hidden layers")
+    ap.add_argument("--hidden", type=int, default=32, choices=(16, 32, 256), help="width of the hidden layers (256: point_mass only, two layers)")
     ap.add_argument("--layers", type=int, default=3, choices=(1, 2, 3), help="hidden layers")
     ap.add_argument("--seed", type=int, default=0, help="of the initial weights")
-    return run(ap.parse_args(argv))
+    o = ap.parse_args(argv)
+    if o.hidden == 256 and o.model != "point_mass":
+        ap.error("--hidden 256 is the point-mass network: use --model point_mass")
+    o.on_round = on_round
+    return run(o)
 
 
 if __name__ == "__main__":

@@ -34,7 +34,7 @@ extern "C" {
 #endif
 
 #define MPPI_ABI_VERSION 5 /* 5: MPPI_TUNE_FUSED_STEP / _ARMED_US / _ARMED_ALWAYS / _PRELAUNCH (no entry point changed), mppi_run_episode / mppi_batch_run_episode
-                              (added; no entry point changed); 4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
+                              (added; no entry point changed), mppi_learner_gradients and the [in, 256, 256, out] learner (added; no entry point changed); 4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
                               _load / _peek, MPPI_TUNE_TRACE (roctx ranges); mppi_set_mlp orders against the last step's stream;
                               3: the 13-state AUV family (MPPI_MODEL_AUV / _NN_AUV, mppi_auv_desc), StaticQuatCost / ElipseCost3D state costs,
                               mppi_auv_pieces, the learner (mppi_learner_*); 2: state_cost_kind / ellipse, transition log, tuning */
@@ -536,7 +536,9 @@ mppi_status mppi_model_rollout_device(mppi_handle *h, const float *x0_dev, int k
 /* ---- the learner of the learned model_base (replaces LearnerBase.train / _train_step, learners/learner_base.py:324-358,
  * 469-496; train_all :146-153) --------------------------------------------------------------------------------------------
  * Full-batch Adam on the mean squared error of the network's prediction against the (normalised) targets, for the
- * reference's Dense networks (nn_model.py:54-60; widths <= 32, 1-4 layers, relu on the hidden layers). The data preparation
+ * reference's Dense networks (nn_model.py:54-60; widths <= 32, 1-4 layers, relu on the hidden layers) and for exactly the network an
+ * MPPI_MODEL_MLP controller rolls out: n_layers = 3, widths = [in, 256, 256, out] with in, out <= 32 (the "wide" learner: every product
+ * on the exact-fp32 matrix-core instruction). Any other shape is MPPI_ERR_UNSUPPORTED. The data preparation
  * (prepare_training_data, normalisation statistics, augmentation) is host bookkeeping in the caller; what runs on the
  * device is forward, loss, backward (the weight-gradient GEMMs over the batch on the matrix cores, exact fp32) and the Adam
  * update — a train loop of many steps needs no host round trip. Its weights are what mppi_config.mlp of an
@@ -553,8 +555,12 @@ mppi_status mppi_learner_set_data(mppi_learner *l, const float *X, const float *
  * beta1 0.9, beta2 0.999, eps 1e-7). loss_first / loss_last (may be NULL): the loss of the first / last step's forward pass. */
 mppi_status mppi_learner_train(mppi_learner *l, int steps, float lr, float beta1, float beta2, float eps, float *loss_first, float *loss_last);
 /* loss of the CURRENT weights on the training set, no update; grads_out (NULL or [n_layers*33*32]: per layer rows 0..31 = dLoss/dW
- * padded to 32 x 32, row 32 = dLoss/db) ; pred_out (NULL or [n, outputs]) */
+ * padded to 32 x 32, row 32 = dLoss/db; widths <= 32 only: on a [in, 256, 256, out] learner a non-NULL grads_out is MPPI_ERR_UNSUPPORTED,
+ * use mppi_learner_gradients) ; pred_out (NULL or [n, outputs]) */
 mppi_status mppi_learner_evaluate(mppi_learner *l, float *loss_out, float *grads_out, float *pred_out);
+/* loss and gradients of the CURRENT weights on the training set, no update; dW[l] is [widths[l] x widths[l+1]] row-major, db[l] [widths[l+1]]
+ * (the layout of mppi_learner_get_weights). Any of loss_out, dW, db may be NULL. Every learner. */
+mppi_status mppi_learner_gradients(mppi_learner *l, float *loss_out, float *const *dW, float *const *db);
 mppi_status mppi_learner_get_weights(mppi_learner *l, float *const *W, float *const *b);
 mppi_status mppi_learner_set_weights(mppi_learner *l, const float *const *W, const float *const *b);
 /* forget the Adam moments and the step count (a new tf.optimizers.Adam, learner_base.py:149) */
@@ -568,6 +574,7 @@ mppi_status mppi_learner_get_step(mppi_learner *l, int *step);
  *     per layer l (in = widths[l], out = widths[l+1]), fp32, compact:  W[in][out] b[out]  mW[in][out] mb[out]  vW[in][out] vb[out]
  *     if has_norm, fp64:  xmean[widths[0]] xstd[widths[0]] ymean[widths[n_layers]] ystd[widths[n_layers]]
  * (the normalisation belongs to the model, not to the learner: the caller passes it in and gets it back; all four NULL = none).
+ * The widths are those mppi_learner_create takes (<= 32, or [in, 256, 256, out]); a file of anything else is MPPI_ERR_IO.
  * mppi_learner_save writes beside the target and renames over it. mppi_learner_load: the learner's layer widths must match (mppi_learner_peek
  * reads them from a file, to create the learner with); weights, both Adam moments and the step count are replaced; *has_norm says whether the
  * file held a normalisation (the four outputs are written only then; they may be NULL). */

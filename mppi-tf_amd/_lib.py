@@ -149,6 +149,7 @@ SIGNATURES = {
     "mppi_learner_set_data": (C.c_int, [_H, FP, FP, C.c_int]),
     "mppi_learner_train": (C.c_int, [_H, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, FP, FP]),
     "mppi_learner_evaluate": (C.c_int, [_H, FP, FP, FP]),
+    "mppi_learner_gradients": (C.c_int, [_H, FP, C.POINTER(FP), C.POINTER(FP)]),
     "mppi_learner_get_weights": (C.c_int, [_H, C.POINTER(FP), C.POINTER(FP)]),
     "mppi_learner_set_weights": (C.c_int, [_H, C.POINTER(FP), C.POINTER(FP)]),
     "mppi_learner_reset_optimizer": (C.c_int, [_H]),
@@ -836,8 +837,9 @@ def shift(U, init, nb):
 
 
 class Learner:
-    """RAII wrapper of one mppi_learner: full-batch Adam on the MSE of a small Dense network, on the GPU (mppi_learner.hip).
-    weights: dict(W=[...], b=[...]) (Keras [in x out] kernels); widths <= 32, 1-4 layers."""
+    """RAII wrapper of one mppi_learner: full-batch Adam on the MSE of a small Dense network, on the GPU (mppi_learner.hip,
+    mppi_learner_wide.hip). weights: dict(W=[...], b=[...]) (Keras [in x out] kernels); widths <= 32 and 1-4 layers, or exactly
+    [in, 256, 256, out] with in, out <= 32 (the network of an MPPI_MODEL_MLP controller)."""
 
     def __init__(self, weights, device=0):
         lib = self.lib = load()
@@ -886,13 +888,14 @@ class Learner:
     def evaluate(self, grads=False, pred=False):
         """loss of the current weights on the training set [, gradients as dict(W=[...], b=[...])] [, predictions]"""
         loss = np.zeros(1, np.float32)
-        g = np.zeros((len(self.Ws), 33, 32), np.float32) if grads else None
         p = np.zeros((self.n, self.widths[-1]), np.float32) if pred else None
-        self._check(self.lib.mppi_learner_evaluate(self.h, fp(loss), fp(g), fp(p)))
+        if pred or not grads:
+            self._check(self.lib.mppi_learner_evaluate(self.h, fp(loss), None, fp(p)))
         out = [float(loss[0])]
-        if grads:
-            out.append(dict(W=[g[l, :self.widths[l], :self.widths[l + 1]].copy() for l in range(len(self.Ws))],
-                            b=[g[l, 32, :self.widths[l + 1]].copy() for l in range(len(self.Ws))]))
+        if grads:  # mppi_learner_gradients: the compact layout of get_weights, for every learner
+            gW, gb = [np.zeros_like(w) for w in self.Ws], [np.zeros_like(b) for b in self.bs]
+            self._check(self.lib.mppi_learner_gradients(self.h, fp(loss), self._ptrs(gW), self._ptrs(gb)))
+            out = [float(loss[0]), dict(W=gW, b=gb)]
         if pred:
             out.append(p)
         return out[0] if len(out) == 1 else tuple(out)

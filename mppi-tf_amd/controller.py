@@ -13,6 +13,8 @@ Arithmetic is fp32 (the C++ reference's DT_FLOAT); the Python reference is fp64.
 
 `scope` arguments are accepted and ignored (TensorFlow name scopes).
 """
+import os
+
 import numpy as np
 
 from . import _lib
@@ -68,6 +70,124 @@ class PointMassModel:
 
     def predict(self, state, action):
         return self.build_step_graph("predict", state, action)
+
+
+class NNPointMassModel:
+    """The learned point-mass model (MPPI_MODEL_MLP: x' = x + denorm(MLP(norm([x; u])))) with the surface of NNAUVModel: the class that
+    holds the weights a learner trains and a Handle(mlp=...) controller rolls out. s = 2a, a in 1..4. hidden: (256, 256) — the network
+    of k_rollout_mlp2 and of the wide learner — or 1 to 3 equal layers of 16 or 32. weights: dict(W=[...], b=[...]); by default
+    glorot-uniform kernels and zero biases (Keras' Dense)."""
+
+    def __init__(self, stateDim=4, actionDim=2, hidden=(256, 256), k=1, name="point_mass_nn_model", weights=None, dt=0.1, seed=0, device=0):
+        self._stateDim, self._actionDim, self._k, self._name, self._dt = int(stateDim), int(actionDim), int(k), name, float(dt)
+        if self._stateDim != 2 * self._actionDim or not 1 <= self._actionDim <= 4:
+            raise ValueError("NNPointMassModel: stateDim == 2 * actionDim, actionDim in 1..4")
+        hidden = tuple(int(h) for h in hidden)
+        if hidden != (256, 256) and not (1 <= len(hidden) <= 3 and len(set(hidden)) == 1 and hidden[0] in (16, 32)):
+            raise ValueError("NNPointMassModel: hidden = (256, 256), or 1 to 3 equal layers of 16 or 32")
+        n_in = self._stateDim + self._actionDim
+        self.Xmean, self.Xstd = np.zeros(n_in), np.ones(n_in)
+        self.Ymean, self.Ystd = np.zeros(self._stateDim), np.ones(self._stateDim)
+        dims = [n_in, *hidden, self._stateDim]
+        if weights is None:
+            rng = np.random.default_rng(seed)
+            lim = [np.sqrt(6.0 / (dims[i] + dims[i + 1])) for i in range(len(dims) - 1)]
+            weights = dict(W=[rng.uniform(-lim[i], lim[i], (dims[i], dims[i + 1])).astype(np.float32) for i in range(len(dims) - 1)],
+                           b=[np.zeros(dims[i + 1], np.float32) for i in range(len(dims) - 1)])
+        self._weights = dict(W=[np.asarray(w, np.float32) for w in weights["W"]], b=[np.asarray(b, np.float32) for b in weights["b"]])
+        if [w.shape for w in self._weights["W"]] != [(dims[i], dims[i + 1]) for i in range(len(dims) - 1)]:
+            raise ValueError("NNPointMassModel: kernels of shapes %s expected" % [(dims[i], dims[i + 1]) for i in range(len(dims) - 1)])
+        self._device, self._h = device, None
+
+    def get_name(self):
+        return self._name
+
+    def get_state_dim(self):
+        return self._stateDim
+
+    def get_action_dim(self):
+        return self._actionDim
+
+    def set_k(self, k):
+        self._k = int(k)
+
+    def set_Xmean_Xstd(self, mean, std):
+        self.Xmean, self.Xstd, self._h = np.asarray(mean, np.float64).reshape(-1), np.asarray(std, np.float64).reshape(-1), None
+
+    def set_Ymean_Ystd(self, mean, std):
+        self.Ymean, self.Ystd, self._h = np.asarray(mean, np.float64).reshape(-1), np.asarray(std, np.float64).reshape(-1), None
+
+    def get_weights(self):
+        out = []
+        for w, b in zip(self._weights["W"], self._weights["b"]):
+            out += [w.copy(), b.copy()]
+        return out
+
+    weights = get_weights
+
+    def update_weights(self, var, msg=False):
+        self._weights = dict(W=[np.asarray(v, np.float32) for v in var[0::2]], b=[np.asarray(v, np.float32) for v in var[1::2]])
+        self._h = None
+
+    def normalisation(self):
+        return dict(xmean=self.Xmean, xstd=self.Xstd, ymean=self.Ymean, ystd=self.Ystd)
+
+    # the flat file of include/mppi_c.h's mppi_learner_save: weights + this model's normalisation, zero Adam slots, step 0
+    def save_params(self, path, step):
+        os.makedirs(path, exist_ok=True)
+        f = os.path.join(path, "weights_step{}".format(step))
+        lrn = _lib.Learner(dict(W=self._weights["W"], b=self._weights["b"]), device=self._device)
+        lrn.save(f, self.normalisation())
+        lrn.close()
+        return f
+
+    def load_params(self, path):
+        lrn, norm = _lib.Learner.from_file(path, device=self._device)
+        w = lrn.get_weights()
+        lrn.close()
+        if [v.shape for v in w["W"]] != [v.shape for v in self._weights["W"]]:
+            raise _lib.MppiError(7, "%s: not a file of this model's layer widths" % path)
+        self._weights, self._h = dict(W=w["W"], b=w["b"]), None
+        if norm is not None:
+            self.set_Xmean_Xstd(norm["xmean"], norm["xstd"])
+            self.set_Ymean_Ystd(norm["ymean"], norm["ystd"])
+
+    def mlp(self):
+        """the dict Handle(mlp=...) and Handle.set_mlp take"""
+        return dict(W=self._weights["W"], b=self._weights["b"], xmean=self.Xmean, xstd=self.Xstd, ymean=self.Ymean, ystd=self.Ystd)
+
+    def _handle(self):
+        if self._h is None:
+            self._h = Handle(k=1, tau=1, s_dim=self._stateDim, a_dim=self._actionDim, dt=self._dt, mlp=self.mlp(), device=self._device)
+        return self._h
+
+    def build_step_graph(self, scope, state, action):
+        return _col(self._handle().model_next(_flat(state, self._stateDim), _flat(action, self._actionDim)))
+
+    def predict(self, state, action):
+        return self.build_step_graph("predict", state, action)
+
+    # data preparation is host bookkeeping (numpy): X = concat(x, u) [n, s+a], Y = x' - x [n, s], the convention of MPPI_MODEL_MLP
+    def prepare_training_data(self, stateT, stateT1, action, norm=True):
+        stateT, stateT1, action = (np.asarray(v, np.float64) for v in (stateT, stateT1, action))
+        X = np.concatenate([stateT, action], axis=1)[..., 0]
+        Y = (stateT1 - stateT)[..., 0]
+        if norm:
+            X, Y = (X - self.Xmean) / self.Xstd, (Y - self.Ymean) / self.Ystd
+        return X, Y
+
+    def prepare_data(self, state, action):
+        data = np.concatenate([np.asarray(state, np.float64), np.asarray(action, np.float64)], axis=1)[..., 0]
+        return (data - self.Xmean) / self.Xstd
+
+    def denormalizeY(self, normY):
+        return normY * self.Ystd + self.Ymean
+
+    def denormalizeX(self, normX):
+        return normX * self.Xstd + self.Xmean
+
+    def next_state(self, state, delta):
+        return np.asarray(state) + np.asarray(delta)
 
 
 class CostBase:

@@ -9,6 +9,8 @@
 //   k_learn_adam     partial tiles summed in fixed order, Adam (Keras form: w -= lr sqrt(1-b2^t)/(1-b1^t) m/(sqrt(v)+eps)),
 //                    the step counter (advanced by the forward pass) and the loss live on the device: a train loop needs no host round trip
 // Deterministic: no float atomics anywhere. All dimensions are padded to 32 (zero weights / activations in the padding).
+// The one wider shape, [in, 256, 256, out] (the network of an MPPI_MODEL_MLP controller), is served by the same object and the same entry
+// points with the kernels of mppi_learner_wide.hip: every entry point below hands a `wide` learner over (mppi_learner.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -16,20 +18,15 @@
 #include <string>
 #include <vector>
 
-#include "mppi_c.h"
+#include "mppi_learner.hip.h"
+
+using namespace mppi_lrn; // W32, kMaxLayers, Net, AdamState
 
 namespace {
 
-constexpr int W32 = 32;            // padded width of every layer
-constexpr int kMaxLayers = 4;
 constexpr int kChunk = 512;        // samples per workgroup of k_learn_grad (r03: 4096 left 8 workgroups on 256 CUs: 180 us per step at n = 8192)
 constexpr int kGradThreads = 256;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Net { // device pointers; weights padded: W[l] is [32][32] ([in][out]), b[l] is [32]
-    float *W[kMaxLayers], *b[kMaxLayers];
-    int n_layers, width[kMaxLayers + 1]; // width[0] = inputs, width[l+1] = outputs of layer l
-};
 
 // one sample per thread: forward, squared error, backward. A[l] ([n][32], l = 0..n_layers-1: the INPUT of layer l) and
 // D[l] ([n][32]: dLoss/d(pre-activation of layer l)) are what the gradient GEMMs read. loss_part[block] = sum of squared errors.
@@ -146,8 +143,6 @@ __global__ __launch_bounds__(kGradThreads) void k_learn_grad(const float *__rest
     for (int e = tid; e < 33 * W32; e += kGradThreads) out[e] = ((tile_s[0][e] + tile_s[1][e]) + tile_s[2][e]) + tile_s[3][e];
 }
 
-struct AdamState { float *m[kMaxLayers], *v[kMaxLayers], *mb[kMaxLayers], *vb[kMaxLayers]; };
-
 // gradient = fixed-order sum of the chunks' partial tiles; Adam as tf.keras.optimizers.Adam applies it (learner_base.py:31,
 // :149): m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; w -= lr sqrt(1-b2^t)/(1-b1^t) m / (sqrt(v) + eps). One workgroup (4 x 1056 parameters).
 // loss_out = the loss of THIS step's forward pass (before the update); grads_out optional.
@@ -187,29 +182,14 @@ __global__ __launch_bounds__(256) void k_learn_adam(const Net net, AdamState st,
 
 } // namespace
 
-struct mppi_learner {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    Net net{};
-    AdamState adam{};
-    std::vector<float *> bufs;
-    float *dX = nullptr, *dY = nullptr, *dA = nullptr, *dD = nullptr, *d_part = nullptr, *d_loss_part = nullptr, *d_loss = nullptr, *d_grads = nullptr;
-    int *d_step = nullptr;
-    int n = 0, cap = 0, chunks = 0, blocks = 0;
-    std::string err;
-};
-
+// the object itself: mppi_learner.hip.h (shared with the wide path, mppi_learner_wide.hip)
 static thread_local std::string g_learner_err;
-static mppi_status lfail(mppi_learner *l, mppi_status st, const std::string &msg)
+mppi_status mppi_lrn_fail(mppi_learner *l, mppi_status st, const std::string &msg)
 {
     if (l) l->err = msg; else g_learner_err = msg;
     return st;
 }
-#define L_TRY(l, expr)                                                                            \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) return lfail((l), MPPI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
+static mppi_status lfail(mppi_learner *l, mppi_status st, const std::string &msg) { return mppi_lrn_fail(l, st, msg); }
 
 extern "C" const char *mppi_learner_last_error(const mppi_learner *l) { return l ? l->err.c_str() : g_learner_err.c_str(); }
 
@@ -219,7 +199,7 @@ extern "C" void mppi_learner_destroy(mppi_learner *l)
     (void)hipSetDevice(l->device);
     if (l->stream) (void)hipStreamSynchronize(l->stream);
     for (float *p : l->bufs) if (p) (void)hipFree(p);
-    float *more[] = {l->dX, l->dY, l->dA, l->dD, l->d_part, l->d_loss_part, l->d_loss, l->d_grads};
+    float *more[] = {l->dX, l->dY, l->dA, l->dD, l->d_part, l->d_loss_part, l->d_loss, l->d_grads, l->wX, l->wA1, l->wA2, l->wD1, l->wD2, l->wD3};
     for (float *p : more) if (p) (void)hipFree(p);
     if (l->d_step) (void)hipFree(l->d_step);
     if (l->stream) (void)hipStreamDestroy(l->stream);
@@ -230,6 +210,7 @@ extern "C" mppi_status mppi_learner_set_weights(mppi_learner *l, const float *co
 {
     if (!l || !W || !b) return l ? lfail(l, MPPI_ERR_INVALID_ARG, "NULL weights") : MPPI_ERR_INVALID_ARG;
     L_TRY(l, hipSetDevice(l->device));
+    if (l->wide) return mppi_lrn_wide_put(l, l->wP, -1, W, b);
     for (int k = 0; k < l->net.n_layers; ++k) {
         const int in = l->net.width[k], out = l->net.width[k + 1];
         std::vector<float> pad(W32 * W32, 0.0f), pb(W32, 0.0f);
@@ -245,6 +226,7 @@ extern "C" mppi_status mppi_learner_reset_optimizer(mppi_learner *l)
 {
     if (!l) return MPPI_ERR_INVALID_ARG;
     L_TRY(l, hipSetDevice(l->device));
+    if (l->wide) return mppi_lrn_wide_reset(l);
     for (int k = 0; k < l->net.n_layers; ++k) {
         L_TRY(l, hipMemset(l->adam.m[k], 0, sizeof(float) * W32 * W32)); L_TRY(l, hipMemset(l->adam.v[k], 0, sizeof(float) * W32 * W32));
         L_TRY(l, hipMemset(l->adam.mb[k], 0, sizeof(float) * W32)); L_TRY(l, hipMemset(l->adam.vb[k], 0, sizeof(float) * W32));
@@ -259,27 +241,31 @@ extern "C" mppi_status mppi_learner_create(int n_layers, const int32_t *widths, 
     if (!out || !widths || !W || !b) return lfail(nullptr, MPPI_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
     if (n_layers < 1 || n_layers > kMaxLayers) return lfail(nullptr, MPPI_ERR_UNSUPPORTED, "learner: 1 to 4 Dense layers");
-    for (int k = 0; k <= n_layers; ++k) if (widths[k] < 1 || widths[k] > W32) return lfail(nullptr, MPPI_ERR_UNSUPPORTED, "learner: layer widths 1..32 (nn_model.py:54-60)");
+    const bool wide = mppi_lrn_wide_shape(n_layers, widths); // [in, 256, 256, out]: the network of an MPPI_MODEL_MLP controller
+    for (int k = 0; !wide && k <= n_layers; ++k)
+        if (widths[k] < 1 || widths[k] > W32) return lfail(nullptr, MPPI_ERR_UNSUPPORTED, "learner: layer widths 1..32 (nn_model.py:54-60), or exactly [in, 256, 256, out] with in, out <= 32");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return lfail(nullptr, MPPI_ERR_NO_DEVICE, "no HIP device visible: the learner has no CPU path"); }
     if (device < 0 || device >= ndev) return lfail(nullptr, MPPI_ERR_NO_DEVICE, "device ordinal out of range");
     mppi_learner *l = new (std::nothrow) mppi_learner();
     if (!l) return lfail(nullptr, MPPI_ERR_ALLOC, "out of host memory");
     l->device = device;
+    l->wide = wide;
     l->net.n_layers = n_layers;
     for (int k = 0; k <= n_layers; ++k) l->net.width[k] = widths[k];
     auto body = [&]() -> mppi_status {
         L_TRY(l, hipSetDevice(device));
         L_TRY(l, hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
         auto alloc = [&](float **p, size_t nfl) -> hipError_t { hipError_t e = hipMalloc((void **)p, sizeof(float) * nfl); if (e == hipSuccess) l->bufs.push_back(*p); return e; };
-        for (int k = 0; k < n_layers; ++k) {
+        for (int k = 0; !wide && k < n_layers; ++k) {
             L_TRY(l, alloc(&l->net.W[k], W32 * W32)); L_TRY(l, alloc(&l->net.b[k], W32));
             L_TRY(l, alloc(&l->adam.m[k], W32 * W32)); L_TRY(l, alloc(&l->adam.v[k], W32 * W32));
             L_TRY(l, alloc(&l->adam.mb[k], W32)); L_TRY(l, alloc(&l->adam.vb[k], W32));
         }
         L_TRY(l, hipMalloc((void **)&l->d_step, sizeof(int)));
         L_TRY(l, hipMalloc((void **)&l->d_loss, sizeof(float)));
-        L_TRY(l, hipMalloc((void **)&l->d_grads, sizeof(float) * kMaxLayers * 33 * W32));
+        if (wide) { mppi_status sw = mppi_lrn_wide_alloc(l); if (sw != MPPI_OK) return sw; }
+        else L_TRY(l, hipMalloc((void **)&l->d_grads, sizeof(float) * kMaxLayers * 33 * W32));
         mppi_status s = mppi_learner_set_weights(l, W, b);
         if (s != MPPI_OK) return s;
         return mppi_learner_reset_optimizer(l);
@@ -295,6 +281,7 @@ extern "C" mppi_status mppi_learner_set_data(mppi_learner *l, const float *X, co
     if (!l || !X || !Y || n <= 0) return l ? lfail(l, MPPI_ERR_INVALID_ARG, "X is [n, in], Y is [n, out], n > 0") : MPPI_ERR_INVALID_ARG;
     L_TRY(l, hipSetDevice(l->device));
     L_TRY(l, hipStreamSynchronize(l->stream));
+    if (l->wide) return mppi_lrn_wide_set_data(l, X, Y, n);
     const int nin = l->net.width[0], nout = l->net.width[l->net.n_layers], L = l->net.n_layers;
     if (n > l->cap) {
         float **ps[] = {&l->dX, &l->dY, &l->dA, &l->dD, &l->d_part, &l->d_loss_part};
@@ -316,6 +303,7 @@ extern "C" mppi_status mppi_learner_set_data(mppi_learner *l, const float *X, co
 
 static mppi_status enqueue_step(mppi_learner *l, float lr, float b1, float b2, float eps, int apply, float *pred_dev)
 {
+    if (l->wide) return mppi_lrn_wide_enqueue_step(l, lr, b1, b2, eps, apply, pred_dev);
     const int L = l->net.n_layers;
     hipLaunchKernelGGL(k_learn_fwd_bwd, dim3(l->blocks), dim3(256), 0, l->stream, l->net, (const float *)l->dX, (const float *)l->dY, l->n, l->dA, l->dD,
                        l->d_loss_part, pred_dev, l->d_step, apply);
@@ -353,6 +341,7 @@ extern "C" mppi_status mppi_learner_evaluate(mppi_learner *l, float *loss_out, f
 {
     if (!l) return MPPI_ERR_INVALID_ARG;
     if (l->n <= 0) return lfail(l, MPPI_ERR_INVALID_ARG, "no data: call mppi_learner_set_data first");
+    if (l->wide && grads_out) return lfail(l, MPPI_ERR_UNSUPPORTED, "grads_out is the 32-padded layout: use mppi_learner_gradients for a [in, 256, 256, out] learner");
     L_TRY(l, hipSetDevice(l->device));
     const int nout = l->net.width[l->net.n_layers];
     float *dp = nullptr;
@@ -370,11 +359,36 @@ extern "C" mppi_status mppi_learner_evaluate(mppi_learner *l, float *loss_out, f
     return st;
 }
 
+// loss and gradients of the CURRENT weights in the compact layout of mppi_learner_get_weights; no update. Serves both kinds of learner.
+extern "C" mppi_status mppi_learner_gradients(mppi_learner *l, float *loss_out, float *const *dW, float *const *db)
+{
+    if (!l) return MPPI_ERR_INVALID_ARG;
+    if (l->n <= 0) return lfail(l, MPPI_ERR_INVALID_ARG, "no data: call mppi_learner_set_data first");
+    L_TRY(l, hipSetDevice(l->device));
+    mppi_status st = enqueue_step(l, 1.0f, 0.9f, 0.999f, 1e-7f, 0, nullptr);
+    if (st != MPPI_OK) return st;
+    L_TRY(l, hipStreamSynchronize(l->stream));
+    if (loss_out) L_TRY(l, hipMemcpy(loss_out, l->d_loss, sizeof(float), hipMemcpyDeviceToHost));
+    if (!dW && !db) return MPPI_OK;
+    if (l->wide) return mppi_lrn_wide_get(l, l->wG, -1, dW, db);
+    const int L = l->net.n_layers;
+    std::vector<float> g((size_t)L * 33 * W32);
+    L_TRY(l, hipMemcpy(g.data(), l->d_grads, sizeof(float) * g.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < L; ++k) {
+        const int in = l->net.width[k], out = l->net.width[k + 1];
+        const float *gk = g.data() + (size_t)k * 33 * W32;
+        if (dW && dW[k]) for (int i = 0; i < in; ++i) for (int o = 0; o < out; ++o) dW[k][(size_t)i * out + o] = gk[i * W32 + o];
+        if (db && db[k]) for (int o = 0; o < out; ++o) db[k][o] = gk[32 * W32 + o];
+    }
+    return MPPI_OK;
+}
+
 extern "C" mppi_status mppi_learner_get_weights(mppi_learner *l, float *const *W, float *const *b)
 {
     if (!l || !W || !b) return l ? lfail(l, MPPI_ERR_INVALID_ARG, "NULL output") : MPPI_ERR_INVALID_ARG;
     L_TRY(l, hipSetDevice(l->device));
     L_TRY(l, hipStreamSynchronize(l->stream));
+    if (l->wide) return mppi_lrn_wide_get(l, l->wP, -1, W, b);
     for (int k = 0; k < l->net.n_layers; ++k) {
         const int in = l->net.width[k], out = l->net.width[k + 1];
         std::vector<float> pad(W32 * W32), pb(W32);
@@ -407,7 +421,8 @@ bool read_header(FILE *f, LearnerFileHeader &hd)
 {
     if (fread(&hd, sizeof(hd), 1, f) != 1 || memcmp(hd.magic, kLearnerMagic, 8) != 0) return false;
     if (hd.n_layers < 1 || hd.n_layers > kMaxLayers) return false;
-    for (int k = 0; k <= hd.n_layers; ++k) if (hd.widths[k] < 1 || hd.widths[k] > W32) return false;
+    if (!mppi_lrn_wide_shape(hd.n_layers, hd.widths))
+        for (int k = 0; k <= hd.n_layers; ++k) if (hd.widths[k] < 1 || hd.widths[k] > W32) return false;
     return hd.step >= 0 && (hd.has_norm == 0 || hd.has_norm == 1);
 }
 } // namespace
@@ -445,6 +460,18 @@ extern "C" mppi_status mppi_learner_save(mppi_learner *l, const char *filename, 
     std::vector<float> pad(W32 * W32), pb(W32);
     for (int k = 0; k < L; ++k) {
         const int in = l->net.width[k], out = l->net.width[k + 1];
+        if (l->wide) { // the same compact bodies, out of the padded images
+            const float *img[3] = {l->wP, l->wM, l->wV};
+            for (int q = 0; q < 3; ++q) {
+                const size_t at = body.size();
+                body.resize(at + (size_t)(in + 1) * out);
+                float *Wq[kMaxLayers] = {}, *bq[kMaxLayers] = {};
+                Wq[k] = body.data() + at; bq[k] = body.data() + at + (size_t)in * out;
+                mppi_status sw = mppi_lrn_wide_get(l, img[q], k, Wq, bq);
+                if (sw != MPPI_OK) return sw;
+            }
+            continue;
+        }
         const float *mats[3] = {l->net.W[k], l->adam.m[k], l->adam.v[k]}, *vecs[3] = {l->net.b[k], l->adam.mb[k], l->adam.vb[k]};
         for (int q = 0; q < 3; ++q) {
             L_TRY(l, hipMemcpy(pad.data(), mats[q], sizeof(float) * W32 * W32, hipMemcpyDeviceToHost));
@@ -494,6 +521,17 @@ extern "C" mppi_status mppi_learner_load(mppi_learner *l, const char *filename, 
     std::vector<float> pad(W32 * W32), pb(W32);
     for (int k = 0; k < L; ++k) {
         const int in = l->net.width[k], out = l->net.width[k + 1];
+        if (l->wide) {
+            float *img[3] = {l->wP, l->wM, l->wV};
+            for (int q = 0; q < 3; ++q) {
+                const float *Wq[kMaxLayers] = {}, *bq[kMaxLayers] = {};
+                Wq[k] = p; bq[k] = p + (size_t)in * out;
+                p += (size_t)(in + 1) * out;
+                mppi_status sw = mppi_lrn_wide_put(l, img[q], k, Wq, bq);
+                if (sw != MPPI_OK) return sw;
+            }
+            continue;
+        }
         float *mats[3] = {l->net.W[k], l->adam.m[k], l->adam.v[k]}, *vecs[3] = {l->net.b[k], l->adam.mb[k], l->adam.vb[k]};
         for (int q = 0; q < 3; ++q) {
             std::fill(pad.begin(), pad.end(), 0.0f); std::fill(pb.begin(), pb.end(), 0.0f); // the padding stays exactly zero

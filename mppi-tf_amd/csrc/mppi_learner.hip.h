@@ -1,0 +1,69 @@
+// mppi_learner.hip.h — what the two translation units of the learner share: the mppi_learner object, its error plumbing and the entry
+// points of the wide path. mppi_learner.hip holds the C-ABI and the narrow learner (every layer padded to 32, one sample per lane);
+// mppi_learner_wide.hip holds the learner of the [in, 256, 256, out] network a MPPI_MODEL_MLP controller rolls out (LDS-tiled GEMMs on
+// v_mfma_f32_32x32x2_f32). One object serves both: `wide` says which set of buffers is alive.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "mppi_c.h"
+
+namespace mppi_lrn {
+
+constexpr int W32 = 32;        // padded width of every layer of the narrow learner, and of the wide learner's two edges
+constexpr int kMaxLayers = 4;
+constexpr int kWideHidden = 256;
+constexpr int kWideLayers = 3;
+// The wide learner keeps weights, both Adam moments, the gradient and every partial gradient tile in ONE padded layout of kWideParams
+// floats: layer l at kWideOff[l] as [rows_l + 1][cols_l] row-major, rows 0..rows_l-1 = W ([in][out]), row rows_l = the bias.
+//   layer 0: [32 + 1][256]   (inputs padded to 32 rows)     layer 1: [256 + 1][256]     layer 2: [256 + 1][32]   (outputs padded to 32 columns)
+constexpr int kWideRows[kWideLayers] = {W32, kWideHidden, kWideHidden};
+constexpr int kWideCols[kWideLayers] = {kWideHidden, kWideHidden, W32};
+constexpr int kWideOff[kWideLayers + 1] = {0, (W32 + 1) * kWideHidden, (W32 + 1) * kWideHidden + (kWideHidden + 1) * kWideHidden,
+                                           (W32 + 1) * kWideHidden + (kWideHidden + 1) * kWideHidden + (kWideHidden + 1) * W32};
+constexpr int kWideParams = kWideOff[kWideLayers];
+
+struct Net { // device pointers; weights padded: W[l] is [32][32] ([in][out]), b[l] is [32]
+    float *W[kMaxLayers], *b[kMaxLayers];
+    int n_layers, width[kMaxLayers + 1]; // width[0] = inputs, width[l+1] = outputs of layer l
+};
+
+struct AdamState { float *m[kMaxLayers], *v[kMaxLayers], *mb[kMaxLayers], *vb[kMaxLayers]; };
+
+} // namespace mppi_lrn
+
+struct mppi_learner {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    mppi_lrn::Net net{};      // the wide learner uses n_layers and width[] only
+    mppi_lrn::AdamState adam{};
+    std::vector<float *> bufs;
+    float *dX = nullptr, *dY = nullptr, *dA = nullptr, *dD = nullptr, *d_part = nullptr, *d_loss_part = nullptr, *d_loss = nullptr, *d_grads = nullptr;
+    int *d_step = nullptr;
+    int n = 0, cap = 0, chunks = 0, blocks = 0;
+    std::string err;
+    // the wide path: parameters, moments and gradient in the padded layout above (in bufs); per-sample buffers (freed by destroy):
+    // wX [n][32] the padded inputs, wA1 / wA2 [n][256] the hidden activations, wD1 / wD2 [n][256] and wD3 [n][32] the deltas
+    bool wide = false;
+    float *wP = nullptr, *wM = nullptr, *wV = nullptr, *wG = nullptr;
+    float *wX = nullptr, *wA1 = nullptr, *wA2 = nullptr, *wD1 = nullptr, *wD2 = nullptr, *wD3 = nullptr;
+};
+
+mppi_status mppi_lrn_fail(mppi_learner *l, mppi_status st, const std::string &msg);
+#define L_TRY(l, expr)                                                                            \
+    do {                                                                                          \
+        hipError_t _e = (expr);                                                                   \
+        if (_e != hipSuccess) return mppi_lrn_fail((l), MPPI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// ---- mppi_learner_wide.hip (the caller has checked its arguments, set the device and, where it matters, synchronised the stream)
+bool mppi_lrn_wide_shape(int n_layers, const int32_t *widths);                 // exactly [1..32, 256, 256, 1..32]
+mppi_status mppi_lrn_wide_alloc(mppi_learner *l);                              // wP, wM, wV, wG
+mppi_status mppi_lrn_wide_set_data(mppi_learner *l, const float *X, const float *Y, int n);
+mppi_status mppi_lrn_wide_enqueue_step(mppi_learner *l, float lr, float b1, float b2, float eps, int apply, float *pred_dev);
+// compact host arrays <-> one padded device image (wP, wM, wV or wG). Layer k alone, or every layer with k = -1. Padding is written as zero.
+mppi_status mppi_lrn_wide_put(mppi_learner *l, float *image, int k, const float *const *W, const float *const *b);
+mppi_status mppi_lrn_wide_get(mppi_learner *l, const float *image, int k, float *const *W, float *const *b);
+mppi_status mppi_lrn_wide_reset(mppi_learner *l);

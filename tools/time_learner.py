@@ -1,0 +1,122 @@
+"""The wide learner's Adam step against the clock, against torch on the same GPU, and against the narrow learner, in one process.
+For the [9, 256, 256, 6] network at n in {1024, 8192, 65536} samples:
+  (a) wide:   Learner.train(200) — 200 full-batch Adam steps enqueued by one call that synchronises once (csrc/mppi_learner_wide.hip);
+  (b) torch:  the same network, loss and optimiser in torch on the same GPU: fp32, torch.backends.cuda.matmul.allow_tf32 = False,
+              torch.optim.Adam(eps=1e-7), 200 steps in one Python loop, synchronised once;
+  (c) narrow: Learner.train(200) of the [16, 32, 32, 32, 13] network at the same n, for scale.
+Each figure is a host clock around work that ends in one device synchronisation, after a warm-up call of the same shape; (a), (b), (c)
+alternate `reps` times and the median is printed in microseconds per step with the spread. The FLOP count of a wide step is the three
+GEMM passes (forward, delta, weight gradient) over the three layers, 3 x 2 n (in 256 + 256 256 + 256 out); the peak it is set against is
+the 157.3 TFLOP/s of the exact-fp32 matrix-core instruction. This is a whole-step rate (nine launches, their gaps included), not a
+kernel's share of peak.
+    tools/time_learner.py [--reps R] [--steps S] [--out FILE] [--dry-run]"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+F32 = np.float32
+WIDE, NARROW = [9, 256, 256, 6], [16, 32, 32, 32, 13]
+NS = (1024, 8192, 65536)
+PEAK_TFLOPS = 157.3
+
+
+def make_net(dims, seed=0):
+    rng = np.random.default_rng(seed)
+    return dict(W=[(rng.uniform(-1, 1, (dims[i], dims[i + 1])) * np.sqrt(6.0 / (dims[i] + dims[i + 1]))).astype(F32) for i in range(len(dims) - 1)],
+                b=[np.zeros(dims[i + 1], F32) for i in range(len(dims) - 1)])
+
+
+def make_data(dims, n):
+    rng = np.random.default_rng(n)
+    X = rng.standard_normal((n, dims[0])).astype(F32)
+    return X, np.tanh(X @ rng.standard_normal((dims[0], dims[-1])) * 0.3).astype(F32)
+
+
+def step_flops(dims, n):
+    return 3 * 2 * n * sum(dims[i] * dims[i + 1] for i in range(len(dims) - 1))
+
+
+def torch_trainer(net, X, Y, lr):
+    import torch
+    torch.backends.cuda.matmul.allow_tf32 = False
+    torch.backends.cudnn.allow_tf32 = False
+    Ws = [torch.tensor(w, device="cuda", requires_grad=True) for w in net["W"]]
+    bs = [torch.tensor(b, device="cuda", requires_grad=True) for b in net["b"]]
+    dX, dY = torch.tensor(X, device="cuda"), torch.tensor(Y, device="cuda")
+    opt = torch.optim.Adam(Ws + bs, lr=lr, eps=1e-7)
+
+    def train(steps):
+        for _ in range(steps):
+            opt.zero_grad(set_to_none=True)
+            h = dX
+            for l in range(len(Ws)):
+                h = torch.addmm(bs[l], h, Ws[l])
+                if l + 1 < len(Ws):
+                    h = torch.relu(h)
+            loss = torch.mean((h - dY) ** 2)
+            loss.backward()
+            opt.step()
+        torch.cuda.synchronize()
+        return float(loss.detach())
+    return train
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--out", help="also write the table to this file")
+    ap.add_argument("--dry-run", action="store_true", help="build the networks and the data, count the operations, time nothing (no GPU)")
+    o = ap.parse_args()
+    if o.dry_run:
+        for n in NS:
+            X, Y = make_data(WIDE, n)
+            print("n=%-6d X %s Y %s  wide step %.4g GFLOP  narrow step %.4g GFLOP" % (n, X.shape, Y.shape, step_flops(WIDE, n) / 1e9, step_flops(NARROW, n) / 1e9))
+        return
+    import torch
+    import mppi_tf_amd as m
+    lr = 1e-3
+    head = ["tools/time_learner.py: %s, %d Adam steps per call, reps %d; medians of a host clock around one call that ends in one synchronisation," % (
+        torch.cuda.get_device_name(0), o.steps, o.reps),
+        "microseconds per step (min-max); wide = [9,256,256,6] on the exact-fp32 matrix cores, torch = the same step in torch fp32 (no tf32), narrow = [16,32,32,32,13];",
+        "TFLOP/s = 3 x 2 n (9*256 + 256*256 + 256*6) per step over the step time (whole step, launch gaps included), peak %.1f" % PEAK_TFLOPS]
+    print("\n".join(head), flush=True)
+    lines = list(head)
+    for n in NS:
+        X, Y = make_data(WIDE, n)
+        Xn, Yn = make_data(NARROW, n)
+        wide, narrow = m.Learner(make_net(WIDE)), m.Learner(make_net(NARROW))
+        wide.set_data(X, Y)
+        narrow.set_data(Xn, Yn)
+        tt = torch_trainer(make_net(WIDE), X, Y, lr)
+        runs = (("wide", lambda: wide.train(o.steps, lr)), ("torch", lambda: tt(o.steps)), ("narrow", lambda: narrow.train(o.steps, lr)))
+        first = {k: f() for k, f in runs}  # warm-up of every shape
+        t = {k: [] for k, _ in runs}
+        for _ in range(o.reps):
+            for k, f in runs:
+                t0 = time.perf_counter()
+                f()
+                t[k].append((time.perf_counter() - t0) / o.steps * 1e6)
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        tf = step_flops(WIDE, n) / (med["wide"] * 1e-6) / 1e12
+        line = ("n=%-6d wide %9.1f us (%.1f-%.1f)  %6.2f TFLOP/s = %4.1f %% of peak   torch %9.1f us (%.1f-%.1f)  torch/wide %5.2fx   narrow %8.1f us (%.1f-%.1f)"
+                "   first-call loss wide %.5f -> %.5f, torch last %.5f" % (
+                    n, med["wide"], min(t["wide"]), max(t["wide"]), tf, 100.0 * tf / PEAK_TFLOPS, med["torch"], min(t["torch"]), max(t["torch"]),
+                    med["torch"] / med["wide"], med["narrow"], min(t["narrow"]), max(t["narrow"]), first["wide"][0], first["wide"][1], first["torch"]))
+        print(line, flush=True)
+        lines.append(line)
+        wide.close()
+        narrow.close()
+    if o.out:
+        os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
+        with open(o.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -15,7 +15,10 @@ positions at step H. The script makes no claim about convergence: it shows the l
     python examples/learn_loop.py --model point_mass --hidden 256
 is the same loop for the point mass: the controller's model is NNPointMassModel (MPPI_MODEL_MLP; --hidden 256: Dense(256) x 2, the network
 of the matrix-core rollout kernel, trained by the wide learner), the plant a k = 1, tau = 1 handle of the analytic point mass (2 actions,
-state (x, vx, y, vy)); the H-step error takes the position components 0 and 2."""
+state (x, vx, y, vy)); the H-step error takes the position components 0 and 2.
+    python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2
+chooses each round's learning rate first: LearnerBase.grid_search trains every rate x every fold as ONE batch of learners (LearnerBatch)
+and the rate with the smallest mean held-out loss trains the model; one more line per round shows the table."""
 import argparse
 import os
 import sys
@@ -84,7 +87,13 @@ def run(o):
         before = one_step_error(model, X, U)
         h_before, windows = h_step_error(cont, fossen, X, U, o.horizon, pos)
         learner.stats()
-        first, last = learner.train_all(learningRate=o.lr, epoch=o.epochs)
+        lr = o.lr
+        if getattr(o, "kfold", 0):
+            # the round's rate by k-fold cross-validation over --lrs: every rate x every fold trains at once, as one batch of learners
+            lr, table = learner.grid_search(o.lrs, k=o.kfold, epoch=o.epochs)
+            print("round %d: %d-fold held-out loss after %d epochs by learning rate: %s -> lr %g" % (
+                r + 1, o.kfold, o.epochs, ", ".join("%g: %.6g" % (a, b) for a, b in zip(o.lrs, table)), lr), flush=True)
+        first, last = learner.train_all(learningRate=lr, epoch=o.epochs)
         cont.set_mlp(model.mlp())
         after = one_step_error(model, X, U)
         h_after, _ = h_step_error(cont, fossen, X, U, o.horizon, pos)
@@ -113,7 +122,15 @@ def main(argv=None, on_round=None):
     ap.add_argument("--hidden", type=int, default=32, choices=(16, 32, 256), help="width of the hidden layers (256: point_mass only, two layers)")
     ap.add_argument("--layers", type=int, default=3, choices=(1, 2, 3), help="hidden layers")
     ap.add_argument("--seed", type=int, default=0, help="of the initial weights")
+    ap.add_argument("--kfold", type=int, default=0, help="K >= 2: choose each round's learning rate among --lrs by K-fold cross-validation (LearnerBase.grid_search)")
+    ap.add_argument("--lrs", type=lambda v: [float(x) for x in v.split(",")], default=None, help="a,b,c: the learning rates --kfold chooses from")
     o = ap.parse_args(argv)
+    if bool(o.kfold) != bool(o.lrs):
+        ap.error("--kfold K and --lrs a,b,c go together")
+    if o.kfold and (o.kfold < 2 or o.kfold > o.steps):
+        ap.error("--kfold: 2 <= K <= --steps")
+    if o.kfold and o.hidden == 256:
+        ap.error("--kfold trains a batch of narrow learners: not with --hidden 256")
     if o.hidden == 256 and o.model != "point_mass":
         ap.error("--hidden 256 is the point-mass network: use --model point_mass")
     o.on_round = on_round

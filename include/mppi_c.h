@@ -34,7 +34,8 @@ extern "C" {
 #endif
 
 #define MPPI_ABI_VERSION 5 /* 5: MPPI_TUNE_FUSED_STEP / _ARMED_US / _ARMED_ALWAYS / _PRELAUNCH (no entry point changed), mppi_run_episode / mppi_batch_run_episode
-                              (added; no entry point changed), mppi_learner_gradients and the [in, 256, 256, out] learner (added; no entry point changed); 4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
+                              (added; no entry point changed), mppi_learner_gradients and the [in, 256, 256, out] learner (added; no entry point changed),
+                              mppi_learner_batch_* (added; no entry point changed); 4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
                               _load / _peek, MPPI_TUNE_TRACE (roctx ranges); mppi_set_mlp orders against the last step's stream;
                               3: the 13-state AUV family (MPPI_MODEL_AUV / _NN_AUV, mppi_auv_desc), StaticQuatCost / ElipseCost3D state costs,
                               mppi_auv_pieces, the learner (mppi_learner_*); 2: state_cost_kind / ellipse, transition log, tuning */
@@ -581,6 +582,44 @@ mppi_status mppi_learner_get_step(mppi_learner *l, int *step);
 mppi_status mppi_learner_save(mppi_learner *l, const char *filename, const double *xmean, const double *xstd, const double *ymean, const double *ystd);
 mppi_status mppi_learner_load(mppi_learner *l, const char *filename, double *xmean, double *xstd, double *ymean, double *ystd, int *has_norm);
 mppi_status mppi_learner_peek(const char *filename, int *n_layers, int32_t *widths /* [5] */);
+
+/* ---- batched learners: B narrow learners in the launches of one (replaces LearnerBase.k_fold_validation / grid_search,
+ * learners/learner_base.py:83-216: k copies of the network, one per fold, each with its own Adam, over a grid of rates).
+ * n_members 1..1024 (else MPPI_ERR_INVALID_ARG); the network is the narrow learner's (n_layers 1..4, widths 1..32, layout of
+ * mppi_learner_create); [in, 256, 256, out] and whatever mppi_learner_create refuses is MPPI_ERR_UNSUPPORTED, checked before the device
+ * is touched. Every member starts from the same W, b.
+ * Data: ONE pool X [n, in], Y [n, out] for all members (mppi_learner_batch_set_data; it resets every split). Member m trains on the
+ * rows train_idx[0..n_train) in that order and reports its held-out loss over test_idx[0..n_test) (mppi_learner_batch_set_split;
+ * indices may repeat, n_train >= 1, n_test >= 0; an index outside [0, n) is MPPI_ERR_INVALID_ARG and nothing changes). Before any
+ * set_split a member trains on rows 0..n-1 and has no test rows.
+ * One step is the lone learner's step for every member, each with its own lr, beta1, beta2, eps ([B] arrays; NULL = 0.9 / 0.999 /
+ * 1e-7); one step counter serves the batch. loss_train[t * B + m] is the loss of step t's forward pass before its update
+ * (mppi_learner_train's loss_first of a one-step call); loss_test[t * B + m] is the loss of the weights AFTER step t's update on the
+ * member's test rows (kfold_step: _train_step, then evaluate), NaN for a member without test rows. mppi_learner_batch_train enqueues
+ * every step on the object's own stream and synchronises once; mppi_learner_batch_evaluate returns both losses of the current weights
+ * without an update.
+ * The contract: member m is bit-identical — weights, loss_train, loss_test — to a lone mppi_learner created with the same weights,
+ * given mppi_learner_set_data(X[train_idx_m], Y[train_idx_m]) and trained with member m's rates (its loss_test: mppi_learner_evaluate of
+ * a lone learner holding the member's weights on X[test_idx_m], Y[test_idx_m]). Members never interact. Deterministic (no float
+ * atomics). The activations are [B][layers][max n_train][32] floats: a large B x n can be MPPI_ERR_ALLOC. Not thread-safe per object.
+ * Errors as the learner's: mppi_learner_batch_last_error(NULL) after a failed create. */
+typedef struct mppi_learner_batch mppi_learner_batch;
+mppi_status mppi_learner_batch_create(int n_members, int n_layers, const int32_t *widths, const float *const *W, const float *const *b,
+                                      int device, mppi_learner_batch **out);
+void mppi_learner_batch_destroy(mppi_learner_batch *lb);
+const char *mppi_learner_batch_last_error(const mppi_learner_batch *lb);
+int mppi_learner_batch_size(const mppi_learner_batch *lb);
+mppi_status mppi_learner_batch_set_data(mppi_learner_batch *lb, const float *X, const float *Y, int n); /* the shared pool */
+mppi_status mppi_learner_batch_set_split(mppi_learner_batch *lb, int member, const int32_t *train_idx, int n_train,
+                                         const int32_t *test_idx, int n_test);
+mppi_status mppi_learner_batch_set_weights(mppi_learner_batch *lb, int member /* -1: every member */, const float *const *W, const float *const *b);
+mppi_status mppi_learner_batch_get_weights(mppi_learner_batch *lb, int member, float *const *W, float *const *b);
+mppi_status mppi_learner_batch_reset_optimizer(mppi_learner_batch *lb);
+mppi_status mppi_learner_batch_get_step(mppi_learner_batch *lb, int *step);
+mppi_status mppi_learner_batch_train(mppi_learner_batch *lb, int steps, const float *lr /* [B] */, const float *beta1, const float *beta2,
+                                     const float *eps /* each [B] or NULL = 0.9 / 0.999 / 1e-7 */,
+                                     float *loss_train /* [steps, B] or NULL */, float *loss_test /* [steps, B] or NULL */);
+mppi_status mppi_learner_batch_evaluate(mppi_learner_batch *lb, float *loss_train /* [B] */, float *loss_test /* [B] */);
 
 #ifdef __cplusplus
 }

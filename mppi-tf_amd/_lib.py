@@ -157,6 +157,19 @@ SIGNATURES = {
     "mppi_learner_save": (C.c_int, [_H, C.c_char_p, DP, DP, DP, DP]),
     "mppi_learner_load": (C.c_int, [_H, C.c_char_p, DP, DP, DP, DP, C.POINTER(C.c_int)]),
     "mppi_learner_peek": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
+    # batched learners (LearnerBase.k_fold_validation / grid_search)
+    "mppi_learner_batch_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(FP), C.POINTER(FP), C.c_int, C.POINTER(_H)]),
+    "mppi_learner_batch_destroy": (None, [_H]),
+    "mppi_learner_batch_last_error": (C.c_char_p, [_H]),
+    "mppi_learner_batch_size": (C.c_int, [_H]),
+    "mppi_learner_batch_set_data": (C.c_int, [_H, FP, FP, C.c_int]),
+    "mppi_learner_batch_set_split": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "mppi_learner_batch_set_weights": (C.c_int, [_H, C.c_int, C.POINTER(FP), C.POINTER(FP)]),
+    "mppi_learner_batch_get_weights": (C.c_int, [_H, C.c_int, C.POINTER(FP), C.POINTER(FP)]),
+    "mppi_learner_batch_reset_optimizer": (C.c_int, [_H]),
+    "mppi_learner_batch_get_step": (C.c_int, [_H, C.POINTER(C.c_int)]),
+    "mppi_learner_batch_train": (C.c_int, [_H, C.c_int, FP, FP, FP, FP, FP, FP]),
+    "mppi_learner_batch_evaluate": (C.c_int, [_H, FP, FP]),
 }
 
 _lib = None
@@ -949,4 +962,109 @@ class Learner:
     def step_count(self):
         v = C.c_int(0)
         self._check(self.lib.mppi_learner_get_step(self.h, C.byref(v)))
+        return int(v.value)
+
+
+class LearnerBatch:
+    """RAII wrapper of one mppi_learner_batch: n_members narrow learners (widths <= 32, 1-4 layers) that share one data pool and
+    step in the same launches (mppi_learner_batch.hip). Every member starts from `weights`, trains on its own rows of the pool
+    (set_split) with its own Adam rates, and is bit-identical to a lone Learner given those rows."""
+
+    def __init__(self, weights, n_members, device=0):
+        lib = self.lib = load()
+        self.Ws = [f32(w) for w in weights["W"]]
+        self.bs = [f32(b).ravel() for b in weights["b"]]
+        self.widths = [self.Ws[0].shape[0]] + [w.shape[1] for w in self.Ws]
+        wd = (C.c_int32 * len(self.widths))(*self.widths)
+        self.h = _H()
+        st = lib.mppi_learner_batch_create(int(n_members), len(self.Ws), wd, Learner._ptrs(self.Ws), Learner._ptrs(self.bs), device, C.byref(self.h))
+        if st != OK:
+            self.h = _H()
+            raise MppiError(st, (lib.mppi_learner_batch_last_error(None) or b"").decode())
+        self.B = int(lib.mppi_learner_batch_size(self.h))
+        self.n = 0
+
+    def _check(self, st):
+        if st != OK:
+            raise MppiError(st, (self.lib.mppi_learner_batch_last_error(self.h) or b"").decode())
+
+    def close(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            self.lib.mppi_learner_batch_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_data(self, X, Y):
+        """the pool every member draws its rows from; resets every split (train on all rows, no test rows)"""
+        X, Y = f32(X, (-1, self.widths[0])), f32(Y, (-1, self.widths[-1]))
+        assert X.shape[0] == Y.shape[0]
+        self._check(self.lib.mppi_learner_batch_set_data(self.h, fp(X), fp(Y), X.shape[0]))
+        self.n = X.shape[0]
+
+    @staticmethod
+    def _idx(idx):
+        a = np.asarray([] if idx is None else idx)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise MppiError(ERR_INVALID_ARG, "row indices must be integers")
+        a = a.astype(np.int64).ravel()
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise MppiError(ERR_INVALID_ARG, "row index outside int32")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def set_split(self, member, train_idx, test_idx=None):
+        """member trains on pool rows train_idx (in that order, repeats allowed) and reports its held-out loss on test_idx"""
+        tr, te = self._idx(train_idx), self._idx(test_idx)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None
+        self._check(self.lib.mppi_learner_batch_set_split(self.h, int(member), ip(tr), tr.size, ip(te), te.size))
+
+    def set_weights(self, weights, member=-1):
+        Ws, bs = [f32(w) for w in weights["W"]], [f32(b).ravel() for b in weights["b"]]
+        if [w.shape for w in Ws] != [w.shape for w in self.Ws] or [b.shape for b in bs] != [b.shape for b in self.bs]:
+            raise MppiError(ERR_INVALID_ARG, "weights of another shape than the batch's network")
+        self._check(self.lib.mppi_learner_batch_set_weights(self.h, int(member), Learner._ptrs(Ws), Learner._ptrs(bs)))
+
+    def get_weights(self, member):
+        Ws, bs = [np.zeros_like(w) for w in self.Ws], [np.zeros_like(b) for b in self.bs]
+        self._check(self.lib.mppi_learner_batch_get_weights(self.h, int(member), Learner._ptrs(Ws), Learner._ptrs(bs)))
+        return dict(W=Ws, b=bs)
+
+    def _per_member(self, v, name):
+        if v is None:
+            return None
+        a = np.asarray(v, np.float32)
+        if a.ndim == 0:
+            return np.full(self.B, a, np.float32)
+        if a.shape != (self.B,):
+            raise MppiError(ERR_INVALID_ARG, "%s: a scalar or %d values, one per member (got shape %s)" % (name, self.B, a.shape))
+        return np.ascontiguousarray(a)
+
+    def train(self, steps, lr, beta1=None, beta2=None, eps=None):
+        """`steps` Adam steps of every member; lr, beta1, beta2, eps: a scalar for all members or one value each (None: Keras' 0.9 /
+        0.999 / 1e-7) -> (loss_train [steps, B]: each step's forward pass before its update, loss_test [steps, B]: the updated weights on
+        the member's test rows, NaN where a member has none)"""
+        steps = int(steps)
+        hp = [self._per_member(v, k) for v, k in ((lr, "lr"), (beta1, "beta1"), (beta2, "beta2"), (eps, "eps"))]
+        if hp[0] is None:
+            raise MppiError(ERR_INVALID_ARG, "lr is required")
+        tr, te = np.zeros((max(steps, 0), self.B), np.float32), np.zeros((max(steps, 0), self.B), np.float32)
+        self._check(self.lib.mppi_learner_batch_train(self.h, steps, *[fp(a) for a in hp], fp(tr), fp(te)))
+        return tr, te
+
+    def evaluate(self):
+        """(loss_train [B], loss_test [B]) of the current weights; no update"""
+        tr, te = np.zeros(self.B, np.float32), np.zeros(self.B, np.float32)
+        self._check(self.lib.mppi_learner_batch_evaluate(self.h, fp(tr), fp(te)))
+        return tr, te
+
+    def reset_optimizer(self):
+        self._check(self.lib.mppi_learner_batch_reset_optimizer(self.h))
+
+    def step_count(self):
+        v = C.c_int(0)
+        self._check(self.lib.mppi_learner_batch_get_step(self.h, C.byref(v)))
         return int(v.value)

@@ -5,13 +5,24 @@ Same method names and argument meaning. What is numeric — the network's forwar
 update — runs on the GPU (mppi_learner.hip through the C-ABI's mppi_learner_*); the bookkeeping around it (replay buffer,
 mean / std of the data, noise augmentation of the inputs) is numpy on the host, as it is host-side Python in the reference.
 The reference's replay buffer is cpprb's ReplayBuffer (a ring of transitions): restated here as three numpy arrays.
-TensorBoard logging, plotting, k-fold grid search are outside the path.
+k_fold_validation / grid_search (learner_base.py:83-216) train their k x R copies of the network as ONE LearnerBatch: every copy steps
+in the same launches (mppi_learner_batch.hip). TensorBoard logging and plotting are outside the path.
 """
 import os
 
 import numpy as np
 
-from ._lib import Learner
+from ._lib import Learner, LearnerBatch
+
+
+def kfold_indices(n, k, seed=0):
+    """k (train_idx, test_idx) pairs over range(n): one permutation split into k folds, the first n % k one row longer
+    (sklearn.model_selection.KFold's fold sizes); fold i is test set i, the other folds in fold order are its training rows."""
+    n, k = int(n), int(k)
+    if k < 2 or k > n:
+        raise ValueError("kfold_indices: 2 <= k <= n (k = %d, n = %d)" % (k, n))
+    folds = np.array_split(np.random.default_rng(seed).permutation(n), k)
+    return [(np.concatenate([folds[j] for j in range(k) if j != i]), folds[i]) for i in range(k)]
 
 
 class ReplayBuffer:
@@ -62,6 +73,7 @@ class LearnerBase:
         self.last_losses = []
         self.logdir = logPath  # where save_params puts weights_step<N> (learner_base.py:40-52 stamps a sub-directory; this keeps the path given)
         self.val_log = []      # (epoch, validate(...)) of the last train(..., val=...)
+        self.kfold_log = None  # dict(train, test) [epoch, R, k] of the last k_fold_validation
 
     # ---- replay buffer (learner_base.py:54-66)
     def load_rb(self, filename):
@@ -128,6 +140,45 @@ class LearnerBase:
         data = self.rb_trans()
         X, y = self.model.prepare_training_data(data["obs"], data["next_obs"], data["act"])
         return self.train(X, y, epoch=epoch, learningRate=learningRate, val=val, writer=writer, augment=augment)
+
+    def k_fold_validation(self, k=10, learningRate=0.1, batchSize=32, epoch=100, val=None, writer=None, seed=0):
+        """learner_base.py:83-127: k copies of the model, copy f trained on every fold but f and tested on fold f after each step, each with
+        its own Adam. learningRate: one rate, or R of them (R x k copies: grid_search's rate axis). All copies are members of ONE
+        LearnerBatch and make their `epoch` steps in one call. -> dict(train=[epoch, R, k], test=[epoch, R, k]): the loss of each step's
+        forward pass before its update, and of the updated weights on the held-out fold; kept in self.kfold_log, and handed epoch by
+        epoch to `writer(e, dict(train=[R, k], test=[R, k]))`. The model and the object's own device learner are not touched (the
+        reference trains copies). batchSize is accepted and ignored, as in train_all; the pairs are train_all's, without augmentation."""
+        if val is not None:
+            raise ValueError("k_fold_validation: trajectory validation of the fold models (val) is not supported")
+        rates = np.atleast_1d(np.asarray(learningRate, np.float32)).ravel()
+        data = self.rb_trans()
+        X, y = self.model.prepare_training_data(data["obs"], data["next_obs"], data["act"])
+        folds = kfold_indices(len(X), k, seed)
+        w = self.model.get_weights()
+        R, k = len(rates), len(folds)
+        batch = LearnerBatch(dict(W=w[0::2], b=w[1::2]), R * k, device=self._device)
+        try:
+            batch.set_data(X, y)
+            for r in range(R):
+                for f, (tr, te) in enumerate(folds):
+                    batch.set_split(r * k + f, tr, te)
+            loss_train, loss_test = batch.train(epoch, np.repeat(rates, k))
+        finally:
+            batch.close()
+        self.kfold_log = dict(train=loss_train.reshape(epoch, R, k), test=loss_test.reshape(epoch, R, k))
+        if callable(writer):
+            for e in range(epoch):
+                writer(e, dict(train=self.kfold_log["train"][e], test=self.kfold_log["test"][e]))
+        return self.kfold_log
+
+    def grid_search(self, learningRates, k=2, epoch=250, seed=0):
+        """learner_base.py:129-216 without its TensorBoard writers and its sigma axis (augmented rows go into the pool by the caller's hand):
+        every rate x every fold in one k_fold_validation -> (best_rate, table); table[r] = the mean over the folds of the last epoch's
+        held-out loss, best_rate its argmin."""
+        rates = [float(r) for r in np.atleast_1d(learningRates).ravel()]
+        log = self.k_fold_validation(k=k, learningRate=rates, epoch=epoch, seed=seed)
+        table = log["test"][-1].astype(np.float64).mean(axis=1)
+        return rates[int(np.argmin(table))], table
 
     def augment_data(self, X, y, samples=5, sigma=0.001, seed=1):
         """every pair `samples` times with N(0, sigma) noise on the inputs (learner_base.py:446-466). The reference then passes the

@@ -9,7 +9,16 @@ alternate `reps` times and the median is printed in microseconds per step with t
 GEMM passes (forward, delta, weight gradient) over the three layers, 3 x 2 n (in 256 + 256 256 + 256 out); the peak it is set against is
 the 157.3 TFLOP/s of the exact-fp32 matrix-core instruction. This is a whole-step rate (nine launches, their gaps included), not a
 kernel's share of peak.
-    tools/time_learner.py [--reps R] [--steps S] [--out FILE] [--dry-run]"""
+    tools/time_learner.py [--reps R] [--steps S] [--out FILE] [--dry-run]
+With --batch B[,B...] it times batched learners instead: for the [16, 32, 32, 32, 13] network at n in --ns (264, 4096) rows, B learners that
+each train on all n rows, as
+  (d) batch:      one LearnerBatch of B members, train(steps) (csrc/mppi_learner_batch.hip: 3 launches per step for all members);
+  (e) sequential: B lone Learners, train(steps) one after another (3 B launches per step of the set);
+  (f) threads:    the same B lone Learners, train(steps) from B host threads at once, each learner on its own stream.
+The same clock, warm-up, alternation and medians; the figure is microseconds per Adam step OF THE WHOLE SET (all B learners advance one
+step). No held-out rows: the lone learners have no test pass to set against one. After the timing every batch member's weights are
+compared with a lone learner's (they made the same number of steps from the same start): the bits must be equal.
+    tools/time_learner.py --batch 10,100 [--ns 264,4096] [--reps R] [--steps S] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -66,13 +75,79 @@ def torch_trainer(net, X, Y, lr):
     return train
 
 
+def time_batch(o):
+    import threading
+    import torch
+    import mppi_tf_amd as m
+    lr = 1e-3
+    head = ["tools/time_learner.py --batch: %s, [16,32,32,32,13], %d Adam steps per call, reps %d; medians of a host clock around calls that end in one" % (
+        torch.cuda.get_device_name(0), o.steps, o.reps),
+        "synchronisation each (every learner enqueues on its own stream); microseconds per Adam step of the whole set of B learners (min-max), alternating rounds;",
+        "batch = one LearnerBatch of B members, sequential = B lone Learners one after another, threads = the same B Learners from B host threads at once"]
+    print("\n".join(head), flush=True)
+    lines = list(head)
+    net = make_net(NARROW)
+    for n in o.ns:
+        X, Y = make_data(NARROW, n)
+        for B in o.batch:
+            batch = m.LearnerBatch(net, B)
+            batch.set_data(X, Y)
+            lone = [m.Learner(net) for _ in range(B)]
+            for l in lone:
+                l.set_data(X, Y)
+
+            def sequential():
+                for l in lone:
+                    l.train(o.steps, lr)
+
+            def threads():
+                ts = [threading.Thread(target=l.train, args=(o.steps, lr)) for l in lone]
+                for th in ts:
+                    th.start()
+                for th in ts:
+                    th.join()
+
+            runs = (("batch", lambda: batch.train(o.steps, lr)), ("sequential", sequential), ("threads", threads))
+            for _, f in runs:  # warm-up of every shape
+                f()
+            t = {k: [] for k, _ in runs}
+            for _ in range(o.reps):
+                for k, f in runs:
+                    t0 = time.perf_counter()
+                    f()
+                    t[k].append((time.perf_counter() - t0) / o.steps * 1e6)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            # the lone learners made two calls per round (sequential, threads), the batch one: bring the batch level, then compare bits
+            batch.train(o.steps * (o.reps + 1), lr)
+            wl = lone[0].get_weights()
+            same = all(np.array_equal(a, b) for mi in (0, B - 1) for key in ("W", "b") for a, b in zip(batch.get_weights(mi)[key], wl[key]))
+            line = ("n=%-5d B=%-4d batch %9.1f us (%.1f-%.1f)   sequential %9.1f us (%.1f-%.1f)  = %5.2fx batch   threads %9.1f us (%.1f-%.1f)  = %5.2fx batch"
+                    "   per learner and step: batch %.2f us, lone %.2f us   members bit-equal to a lone learner after %d steps: %s" % (
+                        n, B, med["batch"], min(t["batch"]), max(t["batch"]), med["sequential"], min(t["sequential"]), max(t["sequential"]),
+                        med["sequential"] / med["batch"], med["threads"], min(t["threads"]), max(t["threads"]), med["threads"] / med["batch"],
+                        med["batch"] / B, med["sequential"] / B, lone[0].step_count(), same and batch.step_count() == lone[0].step_count()))
+            print(line, flush=True)
+            lines.append(line)
+            batch.close()
+            for l in lone:
+                l.close()
+    if o.out:
+        os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
+        with open(o.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=lambda v: [int(x) for x in v.split(",")], help="B[,B...]: time a LearnerBatch of B members against B lone learners")
+    ap.add_argument("--ns", type=lambda v: [int(x) for x in v.split(",")], default=[264, 4096], help="rows of the pool, with --batch")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--out", help="also write the table to this file")
     ap.add_argument("--dry-run", action="store_true", help="build the networks and the data, count the operations, time nothing (no GPU)")
     o = ap.parse_args()
+    if o.batch and not o.dry_run:
+        return time_batch(o)
     if o.dry_run:
         for n in NS:
             X, Y = make_data(WIDE, n)

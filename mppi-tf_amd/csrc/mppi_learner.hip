@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void k_learn_adam(const Net net, AdamState st,
             float *w = is_b ? net.b[l] + col : net.W[l] + row * W32 + col;
             float *m = is_b ? st.mb[l] + col : st.m[l] + row * W32 + col;
             float *v = is_b ? st.vb[l] + col : st.v[l] + row * W32 + col;
-            const float mn = b1 * *m + (1.0f - b1) * g, vn = b2 * *v + (1.0f - b2) * g * g;
+            const float mn = adam_first_moment(b1, *m, g), vn = b2 * *v + (1.0f - b2) * g * g;
             *m = mn; *v = vn;
             *w = *w - lr_t * mn / (sqrtf(vn) + eps);
         }

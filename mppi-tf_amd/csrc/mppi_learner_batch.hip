@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void k_lb_adam(const LbArgs g, const float *__
         if (live) {
             const size_t at = ((size_t)m * L + l) * kTile + e;
             const float mo = g.M[at], vo = g.V[at];
-            const float mn = b1 * mo + (1.0f - b1) * gr, vn = b2 * vo + (1.0f - b2) * gr * gr;
+            const float mn = adam_first_moment(b1, mo, gr), vn = b2 * vo + (1.0f - b2) * gr * gr;
             g.M[at] = mn; g.V[at] = vn;
             g.P[at] = g.P[at] - lr_t * mn / (sqrtf(vn) + eps);
         }

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void k_wide_adam(float *__restrict__ P, float 
             const int t = step[0]; // advanced by this step's forward pass
             const float bc1 = 1.0f - powf(b1, (float)t), bc2 = 1.0f - powf(b2, (float)t);
             const float lr_t = lr * sqrtf(bc2) / bc1;
-            const float mn = b1 * Mo[e] + (1.0f - b1) * gsum, vn = b2 * Vo[e] + (1.0f - b2) * gsum * gsum;
+            const float mn = adam_first_moment(b1, Mo[e], gsum), vn = b2 * Vo[e] + (1.0f - b2) * gsum * gsum;
             Mo[e] = mn; Vo[e] = vn;
             P[e] = P[e] - lr_t * mn / (sqrtf(vn) + eps);
         }

@@ -44,6 +44,42 @@ def numpy_loss_and_grads64(net, X, Y):
     return float(np.mean(e ** 2)), gW, gb
 
 
+def data(dims, n, seed=2):
+    """n rows of standard-normal inputs and targets, fp32 (the data of the gradient tests)"""
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal((n, dims[0])).astype(F32), rng.standard_normal((n, dims[-1])).astype(F32)
+
+
+def numpy_forward64(net, X):
+    """the forward pass in fp64 numpy -> (predictions, the pre-activations of every layer)"""
+    h, zs = X.astype(np.float64), []
+    for l, (W, b) in enumerate(zip(net["W"], net["b"])):
+        zs.append(h @ W.astype(np.float64) + b.astype(np.float64))
+        h = np.maximum(zs[-1], 0.0) if l + 1 < len(net["W"]) else zs[-1]
+    return h, zs
+
+
+def torch_forward(net, X):
+    """the forward pass in torch CPU fp32"""
+    import torch
+    h = torch.tensor(X)
+    for l, (W, b) in enumerate(zip(net["W"], net["b"])):
+        h = h @ torch.tensor(W) + torch.tensor(b)
+        if l + 1 < len(net["W"]):
+            h = torch.relu(h)
+    return h.numpy()
+
+
+def grad_bar(ref):
+    """the gradient tests' bar of one tensor, per entry: rtol 2e-5 and atol 2e-6 of the tensor's largest entry"""
+    ref = np.asarray(ref, np.float64)
+    return 2e-5 * np.abs(ref) + 2e-6 * max(np.abs(ref).max(), 1e-12)
+
+
+def copy_net(net):
+    return dict(W=[w.copy() for w in net["W"]], b=[b.copy() for b in net["b"]])
+
+
 def keras_adam(net, state, gW, gb, t, lr, b1=0.9, b2=0.999, eps=1e-7):
     """tf.keras.optimizers.Adam: m, v, lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), w -= lr_t m / (sqrt(v) + eps); fp32"""
     lr_t = F32(lr) * np.sqrt(F32(1) - F32(b2) ** F32(t)) / (F32(1) - F32(b1) ** F32(t))

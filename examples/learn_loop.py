@@ -18,7 +18,11 @@ of the matrix-core rollout kernel, trained by the wide learner), the plant a k =
 state (x, vx, y, vy)); the H-step error takes the position components 0 and 2.
     python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2
 chooses each round's learning rate first: LearnerBase.grid_search trains every rate x every fold as ONE batch of learners (LearnerBatch)
-and the rate with the smallest mean held-out loss trains the model; one more line per round shows the table."""
+and the rate with the smallest mean held-out loss trains the model; one more line per round shows the table.
+    python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2 --kfold-val
+chooses the rate by what the controller needs instead: every fold's network is rolled H steps open-loop along the windows of the round's
+episode (LearnerBase.validate_fold: all rates x folds in one launch) and the rate with the smallest mean H-step error wins; a second
+line per round shows that table."""
 import argparse
 import os
 import sys
@@ -57,6 +61,15 @@ def h_step_error(cont, plant, X, U, H, pos=(0, 1, 2)):
     return float(np.mean(np.linalg.norm(Xm[-1][:, pos].astype(np.float64) - Xp[-1][:, pos].astype(np.float64), axis=1))), n
 
 
+def windows_val(X, U, H):
+    """the episode's windows as LearnerBase's val = (gtTrajs [n, H+1, s], actionSeqs [n, H+1, a]): window t holds X[t..t+H] and U[t..t+H-1]
+    (the last action row of a trajectory is never applied: zeros)"""
+    n = U.shape[0] - H + 1
+    gt = np.stack([X[t:t + H + 1] for t in range(n)])
+    act = np.stack([np.concatenate([U[t:t + H], np.zeros((1, U.shape[1]), U.dtype)]) for t in range(n)])
+    return gt, act
+
+
 def run(o):
     """-> (the learner, the rounds' episodes [(X, U, C)], the rounds' printed figures [(mean cost, error before, error after, loss first,
     loss last[, H-step error before, H-step error after: when the episode holds a window of H steps])])"""
@@ -90,9 +103,16 @@ def run(o):
         lr = o.lr
         if getattr(o, "kfold", 0):
             # the round's rate by k-fold cross-validation over --lrs: every rate x every fold trains at once, as one batch of learners
-            lr, table = learner.grid_search(o.lrs, k=o.kfold, epoch=o.epochs)
+            by_val = getattr(o, "kfold_val", False)
+            lr, table = learner.grid_search(o.lrs, k=o.kfold, epoch=o.epochs, val=windows_val(X, U, o.horizon) if by_val else None,
+                                            by="val" if by_val else "test")
+            held_out = learner.kfold_log["test"][-1].astype(np.float64).mean(axis=1)
             print("round %d: %d-fold held-out loss after %d epochs by learning rate: %s -> lr %g" % (
-                r + 1, o.kfold, o.epochs, ", ".join("%g: %.6g" % (a, b) for a, b in zip(o.lrs, table)), lr), flush=True)
+                r + 1, o.kfold, o.epochs, ", ".join("%g: %.6g" % (a, b) for a, b in zip(o.lrs, held_out)), lr), flush=True)
+            if by_val:
+                print("round %d: %d-fold H-step open-loop squared error (H = %d, %d windows) after %d epochs by learning rate: %s -> lr %g" % (
+                    r + 1, o.kfold, o.horizon, windows, 10 * ((o.epochs - 1) // 10) + 1,
+                    ", ".join("%g: %.6g" % (a, b) for a, b in zip(o.lrs, table)), lr), flush=True)
         first, last = learner.train_all(learningRate=lr, epoch=o.epochs)
         cont.set_mlp(model.mlp())
         after = one_step_error(model, X, U)
@@ -124,7 +144,10 @@ def main(argv=None, on_round=None):
     ap.add_argument("--seed", type=int, default=0, help="of the initial weights")
     ap.add_argument("--kfold", type=int, default=0, help="K >= 2: choose each round's learning rate among --lrs by K-fold cross-validation (LearnerBase.grid_search)")
     ap.add_argument("--lrs", type=lambda v: [float(x) for x in v.split(",")], default=None, help="a,b,c: the learning rates --kfold chooses from")
+    ap.add_argument("--kfold-val", action="store_true", help="with --kfold: choose the rate by the folds' H-step open-loop error on the round's episode (LearnerBase.validate_fold)")
     o = ap.parse_args(argv)
+    if o.kfold_val and (not o.kfold or o.steps < o.horizon):
+        ap.error("--kfold-val goes with --kfold and needs --steps >= --horizon")
     if bool(o.kfold) != bool(o.lrs):
         ap.error("--kfold K and --lrs a,b,c go together")
     if o.kfold and (o.kfold < 2 or o.kfold > o.steps):

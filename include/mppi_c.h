@@ -621,6 +621,32 @@ mppi_status mppi_learner_batch_train(mppi_learner_batch *lb, int steps, const fl
                                      float *loss_train /* [steps, B] or NULL */, float *loss_test /* [steps, B] or NULL */);
 mppi_status mppi_learner_batch_evaluate(mppi_learner_batch *lb, float *loss_train /* [B] */, float *loss_test /* [B] */);
 
+/* ---- trajectory validation of the members (LearnerBase.validate_fold; learner_base.py:181-188, 211-216 roll each fold's model along
+ * held-out action sequences every tenth epoch): every member's network, as the learned model `model` describes it, rolled open-loop
+ * along n action sequences of T steps in ONE launch on the batch's stream, one synchronisation. Host pointers; layouts as
+ * mppi_model_rollout: x0 [kx, s_dim] with kx = 1 (shared) or n, V [T, n, a_dim], G [T+1, n, s_dim] the ground truth.
+ *   X_out[m, 0, i] = x0, X_out[m, t+1, i] = model_m(X_out[m, t, i], V[t, i]): bit for bit what mppi_model_rollout returns on a lone
+ *     handle of that model kind holding member m's weights and this normalisation (the reference-ordered evaluation of mppi_model_step).
+ *   sse_out[m, j] = sum over t = 0..T and i of (X[m, t, i, j] - G[t, i, j])^2: fp32 per trajectory (t ascending) and per 64 trajectories
+ *     (a fixed butterfly), then the blocks of 64 in order in fp64. A member whose trajectories overflow reports a non-finite sse of its
+ *     own; the other members are unaffected. Deterministic.
+ * The batch's weights, Adam moments, data, splits and step counter are neither written nor, but for the weights, read.
+ * Refused before the device is touched, the batch stays usable: MPPI_ERR_INVALID_ARG for model, x0 or V NULL, both outputs NULL, sse_out
+ * without G, n < 1, T < 1, n * T > 2^30, kx not 1 or n, an xstd entry equal to 0; MPPI_ERR_UNSUPPORTED for a model_kind outside the three
+ * and for a network whose first / last width is not the kind's (MPPI_MODEL_MLP: s_dim + a_dim -> s_dim with s_dim = 2 a_dim, a_dim <= 4;
+ * MPPI_MODEL_NN_AUV: 16 -> 13 and MPPI_MODEL_NN_AUV_SPEED: 15 -> 6, both s_dim = 13, a_dim = 6). */
+typedef struct {
+    int32_t model_kind;          /* MPPI_MODEL_MLP | MPPI_MODEL_NN_AUV | MPPI_MODEL_NN_AUV_SPEED */
+    int32_t s_dim, a_dim;
+    float   dt;                  /* NN_AUV_SPEED only */
+    const float *xmean, *xstd;   /* [net inputs]; NULL = 0 / 1 */
+    const float *ymean, *ystd;   /* [net outputs]; NULL = 0 / 1 */
+} mppi_learner_model;
+mppi_status mppi_learner_batch_rollout(mppi_learner_batch *lb, const mppi_learner_model *model,
+                                       const float *x0 /* [kx, s], kx in {1, n} */, int kx, const float *V /* [T, n, a] */,
+                                       const float *G /* [T+1, n, s] or NULL */, int n, int T,
+                                       double *sse_out /* [B, s] or NULL; needs G */, float *X_out /* [B, T+1, n, s] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

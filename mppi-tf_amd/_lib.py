@@ -60,6 +60,12 @@ class Config(C.Structure):
                 ("auv", C.POINTER(AuvDesc)), ("quat_Q", FP), ("ellipse3d", FP)]
 
 
+class LearnerModel(C.Structure):
+    """mppi_learner_model: the learned model around a batch's network (mppi_learner_batch_rollout)"""
+    _fields_ = [("model_kind", C.c_int32), ("s_dim", C.c_int32), ("a_dim", C.c_int32), ("dt", C.c_float),
+                ("xmean", FP), ("xstd", FP), ("ymean", FP), ("ystd", FP)]
+
+
 class Collectives(C.Structure):
     """mppi_collectives: the caller's all-gather / all-reduce with ncclAllGather's / ncclAllReduce's signatures + the communicator"""
     _fields_ = [("all_gather", C.c_void_p), ("all_reduce", C.c_void_p), ("comm", C.c_void_p)]
@@ -170,6 +176,8 @@ SIGNATURES = {
     "mppi_learner_batch_get_step": (C.c_int, [_H, C.POINTER(C.c_int)]),
     "mppi_learner_batch_train": (C.c_int, [_H, C.c_int, FP, FP, FP, FP, FP, FP]),
     "mppi_learner_batch_evaluate": (C.c_int, [_H, FP, FP]),
+    # ... their trajectory validation (LearnerBatch.rollout, LearnerBase.validate_fold)
+    "mppi_learner_batch_rollout": (C.c_int, [_H, C.POINTER(LearnerModel), FP, C.c_int, FP, FP, C.c_int, C.c_int, DP, FP]),
 }
 
 _lib = None
@@ -1068,3 +1076,55 @@ class LearnerBatch:
         v = C.c_int(0)
         self._check(self.lib.mppi_learner_batch_get_step(self.h, C.byref(v)))
         return int(v.value)
+
+    # ---- trajectory validation (mppi_learner_batch_rollout, include/mppi_c.h)
+    _KINDS = {"mlp": MODEL_MLP, "nnauv": MODEL_NN_AUV, "nnauv_speed": MODEL_NN_AUV_SPEED}
+
+    @classmethod
+    def model_desc(cls, model):
+        """dict(kind, s_dim, a_dim[, dt, xmean, xstd, ymean, ystd]) of `model`: such a dict itself (kind: MPPI_MODEL_* or "mlp" / "nnauv" /
+        "nnauv_speed"), or a model object — NNAUVModel, NNAUVModelSpeed, NNPointMassModel — from which these are read"""
+        if isinstance(model, dict):
+            d = dict(model)
+        else:
+            speed = hasattr(model, "to_euler")
+            s, a = int(model.get_state_dim()), int(model.get_action_dim())
+            kind = MODEL_NN_AUV_SPEED if speed else (MODEL_NN_AUV if s == 13 else MODEL_MLP)
+            d = dict(kind=kind, s_dim=s, a_dim=a, dt=float(getattr(model, "_dt", 0.1)), **model.normalisation())
+        d["kind"] = cls._KINDS.get(d["kind"], d["kind"])
+        return d
+
+    def rollout(self, model, x0, V, gt=None, trajectories=False):
+        """Every member's network rolled open-loop as the learned model `model` (model_desc) along the action sequences V [T, n, a] from
+        x0 [s] or [n, s], in ONE launch -> dict(sse [B, s] float64: the summed squared error against the ground truth gt [T+1, n, s], row 0
+        included (None without gt); X [B, T+1, n, s] float32 with trajectories=True: member m's is bit for bit
+        Handle(member m's weights).model_rollout(x0, V)). The batch itself does not change. Shapes are checked here: ValueError."""
+        d = self.model_desc(model)
+        s, a = int(d["s_dim"]), int(d["a_dim"])
+        V, x0 = np.asarray(V, dtype=np.float32), np.asarray(x0, dtype=np.float32)
+        if V.ndim != 3 or V.shape[2] != a or V.shape[0] < 1 or V.shape[1] < 1:
+            raise ValueError("V must have shape (T, n, %d) with T, n >= 1, not %s" % (a, V.shape))
+        T, n = V.shape[0], V.shape[1]
+        if x0.shape not in [(s,), (1, s), (n, s)]:
+            raise ValueError("x0 must have shape (%d,), (1, %d) or (%d, %d), not %s" % (s, s, n, s, x0.shape))
+        if gt is None and not trajectories:
+            raise ValueError("rollout: nothing to return without gt and without trajectories")
+        x0, V = np.ascontiguousarray(x0).reshape(-1, s), np.ascontiguousarray(V)
+        G = None
+        if gt is not None:
+            G = np.ascontiguousarray(np.asarray(gt, dtype=np.float32))
+            if G.shape != (T + 1, n, s):
+                raise ValueError("gt must have shape (%d, %d, %d), not %s" % (T + 1, n, s, G.shape))
+        held = {k: (f32(d[k]).ravel() if d.get(k) is not None else None) for k in ("xmean", "xstd", "ymean", "ystd")}
+        for k, v in held.items():  # the library reads widths[0] / widths[-1] entries: the network's own widths, which it holds the kind to
+            if v is not None and v.size != (self.widths[0] if k[0] == "x" else self.widths[-1]):
+                raise ValueError("%s must have %d entries, not %d" % (k, self.widths[0] if k[0] == "x" else self.widths[-1], v.size))
+        desc = LearnerModel(int(d["kind"]), s, a, float(d.get("dt") or 0.0), *[fp(held[k]) for k in ("xmean", "xstd", "ymean", "ystd")])
+        sse = np.zeros((self.B, s), np.float64) if G is not None else None
+        X = np.zeros((self.B, T + 1, n, s), np.float32) if trajectories else None
+        self._check(self.lib.mppi_learner_batch_rollout(self.h, C.byref(desc), fp(x0), x0.shape[0], fp(V), fp(G), n, T,
+                                                        sse.ctypes.data_as(DP) if sse is not None else None, fp(X)))
+        out = dict(sse=sse)
+        if trajectories:
+            out["X"] = X
+        return out

@@ -40,7 +40,25 @@ __device__ __forceinline__ float adam_first_moment(float b1, float m, float g)
     return (float)((double)b1 * (double)m + (1.0 - (double)b1) * (double)g);
 }
 
+// What k_lb_rollout takes, by value (mppi_learner_rollout.hip; filled by mppi_learner_batch_rollout, which has checked every field):
+// the batch's weight block, the model around the network and the trajectories. Device pointers.
+constexpr int kRollThreads = 64;  // one lane per trajectory, one wave per workgroup
+constexpr int kRollMaxIn = 16, kRollMaxOut = 13; // the widest network input / output of the three model kinds
+struct LbRollout {
+    const float *P;                       // [B][L][33][32]
+    int n_layers, width[kMaxLayers + 1];
+    int kind, s, a;                       // MPPI_MODEL_MLP | _NN_AUV | _NN_AUV_SPEED; the state and action widths the kind fixes
+    float dt;
+    float xmean[kRollMaxIn], xstd[kRollMaxIn], ymean[kRollMaxOut], ystd[kRollMaxOut];
+    const float *x0, *V, *G;              // [kx][s], [T][n][a], [T+1][n][s] or NULL
+    float *X, *part;                      // [B][T+1][n][s] or NULL; [B][blocks][s] (with G)
+    int kx, n, T, blocks;                 // blocks = ceil(n / kRollThreads)
+};
+
 } // namespace mppi_lrn
+
+// grid (blocks, B) on `st`; hipErrorInvalidValue for a (kind, s, a) no instance serves
+hipError_t mppi_lrn_launch_rollout(const mppi_lrn::LbRollout &r, int B, hipStream_t st);
 
 struct mppi_learner {
     int device = 0;

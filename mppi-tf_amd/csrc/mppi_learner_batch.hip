@@ -279,6 +279,8 @@ struct mppi_learner_batch {
     float *d_hp = nullptr, *d_eval = nullptr, *d_hist = nullptr;            // [B][4]; [2][B]; [2][hist_cap]
     size_t hist_cap = 0;
     int max_test = 0;
+    float *d_roll = nullptr; // mppi_learner_batch_rollout's inputs, trajectories and partials: one buffer, grown on demand
+    size_t roll_cap = 0;
     std::string err;
 };
 
@@ -369,7 +371,7 @@ extern "C" void mppi_learner_batch_destroy(mppi_learner_batch *lb)
     if (lb->stream) (void)hipStreamSynchronize(lb->stream);
     free_split_buffers(lb);
     lb_free(&lb->g.P); lb_free(&lb->g.M); lb_free(&lb->g.V); lb_free(&lb->g.step);
-    lb_free(&lb->dX); lb_free(&lb->dY); lb_free(&lb->d_counts); lb_free(&lb->d_hp); lb_free(&lb->d_eval); lb_free(&lb->d_hist);
+    lb_free(&lb->dX); lb_free(&lb->dY); lb_free(&lb->d_counts); lb_free(&lb->d_hp); lb_free(&lb->d_eval); lb_free(&lb->d_hist); lb_free(&lb->d_roll);
     if (lb->stream) (void)hipStreamDestroy(lb->stream);
     delete lb;
 }
@@ -609,5 +611,100 @@ extern "C" mppi_status mppi_learner_batch_evaluate(mppi_learner_batch *lb, float
     if (loss_train) B_TRY(lb, hipMemcpy(loss_train, lb->d_eval, sizeof(float) * B, hipMemcpyDeviceToHost));
     if (test) B_TRY(lb, hipMemcpy(loss_test, lb->d_eval + B, sizeof(float) * B, hipMemcpyDeviceToHost));
     else if (loss_test) for (int m = 0; m < B; ++m) loss_test[m] = std::numeric_limits<float>::quiet_NaN();
+    return MPPI_OK;
+}
+
+// ---- trajectory validation: every member's network rolled open-loop in one launch (k_lb_rollout, mppi_learner_rollout.hip)
+namespace {
+
+// the network's first and last width the model kind asks for; 0: not one of the three kinds, -1: s_dim / a_dim do not fit the kind
+int roll_widths(const mppi_learner_model *mo, int *nin, int *nout)
+{
+    switch (mo->model_kind) {
+    case MPPI_MODEL_MLP:
+        if (mo->a_dim < 1 || mo->a_dim > 4 || mo->s_dim != 2 * mo->a_dim) return -1;
+        *nin = mo->s_dim + mo->a_dim; *nout = mo->s_dim;
+        return 1;
+    case MPPI_MODEL_NN_AUV:
+    case MPPI_MODEL_NN_AUV_SPEED:
+        if (mo->s_dim != 13 || mo->a_dim != 6) return -1;
+        *nin = mo->model_kind == MPPI_MODEL_NN_AUV ? 16 : 15; *nout = mo->model_kind == MPPI_MODEL_NN_AUV ? 13 : 6;
+        return 1;
+    default:
+        return 0;
+    }
+}
+
+} // namespace
+
+extern "C" mppi_status mppi_learner_batch_rollout(mppi_learner_batch *lb, const mppi_learner_model *model, const float *x0, int kx, const float *V,
+                                                  const float *G, int n, int T, double *sse_out, float *X_out)
+{
+    if (!lb) return MPPI_ERR_INVALID_ARG;
+    const std::string who = "mppi_learner_batch_rollout: ";
+    // every refusal before the device is touched
+    if (!model || !x0 || !V) return bfail(lb, MPPI_ERR_INVALID_ARG, who + "model, x0 [kx, s_dim] and V [T, n, a_dim] are required: NULL pointer");
+    if (!sse_out && !X_out) return bfail(lb, MPPI_ERR_INVALID_ARG, who + "sse_out and X_out are both NULL");
+    if (sse_out && !G) return bfail(lb, MPPI_ERR_INVALID_ARG, who + "sse_out needs the ground truth G [T+1, n, s_dim]");
+    if (n < 1 || T < 1) return bfail(lb, MPPI_ERR_INVALID_ARG, who + "n and T must be >= 1");
+    if ((size_t)n * (size_t)T > ((size_t)1 << 30)) return bfail(lb, MPPI_ERR_INVALID_ARG, who + "n * T must not exceed 2^30");
+    if (kx != 1 && kx != n) return bfail(lb, MPPI_ERR_INVALID_ARG, who + "x0 is [kx, s_dim] with kx in {1, n}");
+    int nin = 0, nout = 0;
+    const int fit = roll_widths(model, &nin, &nout);
+    if (fit == 0) return bfail(lb, MPPI_ERR_UNSUPPORTED, who + "model_kind must be MPPI_MODEL_MLP, MPPI_MODEL_NN_AUV or MPPI_MODEL_NN_AUV_SPEED");
+    const int L = lb->g.n_layers, B = lb->B;
+    if (fit < 0 || lb->g.width[0] != nin || lb->g.width[L] != nout)
+        return bfail(lb, MPPI_ERR_UNSUPPORTED, who + "the batch's network is [" + std::to_string(lb->g.width[0]) + " -> " + std::to_string(lb->g.width[L]) +
+            "]: MPPI_MODEL_MLP takes s_dim + a_dim -> s_dim with s_dim = 2 a_dim, a_dim <= 4; MPPI_MODEL_NN_AUV 16 -> 13 and MPPI_MODEL_NN_AUV_SPEED "
+            "15 -> 6, both with s_dim = 13, a_dim = 6");
+    LbRollout r{};
+    for (int j = 0; j < kRollMaxIn; ++j) { r.xmean[j] = 0.0f; r.xstd[j] = 1.0f; }
+    for (int j = 0; j < kRollMaxOut; ++j) { r.ymean[j] = 0.0f; r.ystd[j] = 1.0f; }
+    for (int j = 0; j < nin; ++j) {
+        if (model->xmean) r.xmean[j] = model->xmean[j];
+        if (model->xstd) r.xstd[j] = model->xstd[j];
+        if (r.xstd[j] == 0.0f) return bfail(lb, MPPI_ERR_INVALID_ARG, who + "xstd[" + std::to_string(j) + "] is 0: the inputs are divided by it");
+    }
+    for (int j = 0; j < nout; ++j) {
+        if (model->ymean) r.ymean[j] = model->ymean[j];
+        if (model->ystd) r.ystd[j] = model->ystd[j];
+    }
+    const size_t s = (size_t)model->s_dim, a = (size_t)model->a_dim, rows = (size_t)n * (size_t)T, blocks = ((size_t)n + kRollThreads - 1) / kRollThreads;
+    r.P = lb->g.P; r.n_layers = L;
+    for (int k = 0; k <= L; ++k) r.width[k] = lb->g.width[k];
+    r.kind = model->model_kind; r.s = model->s_dim; r.a = model->a_dim; r.dt = model->dt;
+    r.kx = kx; r.n = n; r.T = T; r.blocks = (int)blocks;
+    B_TRY(lb, hipSetDevice(lb->device));
+    // one buffer on the batch, carved into x0, V, G, the partials and X (each part a multiple of 64 floats: 256-byte starts)
+    const auto pad = [](size_t c) { return (c + 63) & ~(size_t)63; };
+    const size_t c_x = pad((size_t)kx * s), c_V = pad(rows * a), c_G = G ? pad((rows + n) * s) : 0, c_part = G ? pad((size_t)B * blocks * s) : 0,
+                 c_X = X_out ? pad((size_t)B * (rows + n) * s) : 0, total = c_x + c_V + c_G + c_part + c_X;
+    if (total > lb->roll_cap) {
+        B_TRY(lb, hipStreamSynchronize(lb->stream));
+        lb_free(&lb->d_roll); lb->roll_cap = 0;
+        if (mppi_status st = lb_alloc(lb, &lb->d_roll, total, "the trajectories [B][T+1][n][s_dim] and their inputs"); st != MPPI_OK) return st;
+        lb->roll_cap = total;
+    }
+    float *dx = lb->d_roll, *dV = dx + c_x, *dG = G ? dV + c_V : nullptr, *dpart = G ? dV + c_V + c_G : nullptr, *dX = X_out ? dV + c_V + c_G + c_part : nullptr;
+    hipStream_t q = lb->stream;
+    B_TRY(lb, hipMemcpyAsync(dx, x0, sizeof(float) * (size_t)kx * s, hipMemcpyHostToDevice, q));
+    B_TRY(lb, hipMemcpyAsync(dV, V, sizeof(float) * rows * a, hipMemcpyHostToDevice, q));
+    if (G) B_TRY(lb, hipMemcpyAsync(dG, G, sizeof(float) * (rows + n) * s, hipMemcpyHostToDevice, q));
+    r.x0 = dx; r.V = dV; r.G = dG; r.X = dX; r.part = dpart;
+    if (hipError_t e = mppi_lrn_launch_rollout(r, B, q); e != hipSuccess) {
+        (void)hipStreamSynchronize(q);
+        return bfail(lb, MPPI_ERR_HIP, who + hipGetErrorString(e));
+    }
+    std::vector<float> part(sse_out ? (size_t)B * blocks * s : 0);
+    if (sse_out) B_TRY(lb, hipMemcpyAsync(part.data(), dpart, sizeof(float) * part.size(), hipMemcpyDeviceToHost, q));
+    if (X_out) B_TRY(lb, hipMemcpyAsync(X_out, dX, sizeof(float) * (size_t)B * (rows + n) * s, hipMemcpyDeviceToHost, q));
+    B_TRY(lb, hipStreamSynchronize(q));
+    if (sse_out) // the blocks of a member in block order, in fp64
+        for (int m = 0; m < B; ++m)
+            for (size_t j = 0; j < s; ++j) {
+                double acc = 0.0;
+                for (size_t b = 0; b < blocks; ++b) acc += (double)part[((size_t)m * blocks + b) * s + j];
+                sse_out[(size_t)m * s + j] = acc;
+            }
     return MPPI_OK;
 }

@@ -6,7 +6,8 @@ update — runs on the GPU (mppi_learner.hip through the C-ABI's mppi_learner_*)
 mean / std of the data, noise augmentation of the inputs) is numpy on the host, as it is host-side Python in the reference.
 The reference's replay buffer is cpprb's ReplayBuffer (a ring of transitions): restated here as three numpy arrays.
 k_fold_validation / grid_search (learner_base.py:83-216) train their k x R copies of the network as ONE LearnerBatch: every copy steps
-in the same launches (mppi_learner_batch.hip). TensorBoard logging and plotting are outside the path.
+in the same launches (mppi_learner_batch.hip), and validate_fold rolls every copy along held-out trajectories in one more
+(mppi_learner_rollout.hip). TensorBoard logging and plotting are outside the path.
 """
 import os
 
@@ -73,7 +74,7 @@ class LearnerBase:
         self.last_losses = []
         self.logdir = logPath  # where save_params puts weights_step<N> (learner_base.py:40-52 stamps a sub-directory; this keeps the path given)
         self.val_log = []      # (epoch, validate(...)) of the last train(..., val=...)
-        self.kfold_log = None  # dict(train, test) [epoch, R, k] of the last k_fold_validation
+        self.kfold_log = None  # dict(train, test [epoch, R, k][, val [ceil(epoch / 10), R, k]]) of the last k_fold_validation
 
     # ---- replay buffer (learner_base.py:54-66)
     def load_rb(self, filename):
@@ -144,12 +145,18 @@ class LearnerBase:
     def k_fold_validation(self, k=10, learningRate=0.1, batchSize=32, epoch=100, val=None, writer=None, seed=0):
         """learner_base.py:83-127: k copies of the model, copy f trained on every fold but f and tested on fold f after each step, each with
         its own Adam. learningRate: one rate, or R of them (R x k copies: grid_search's rate axis). All copies are members of ONE
-        LearnerBatch and make their `epoch` steps in one call. -> dict(train=[epoch, R, k], test=[epoch, R, k]): the loss of each step's
-        forward pass before its update, and of the updated weights on the held-out fold; kept in self.kfold_log, and handed epoch by
-        epoch to `writer(e, dict(train=[R, k], test=[R, k]))`. The model and the object's own device learner are not touched (the
-        reference trains copies). batchSize is accepted and ignored, as in train_all; the pairs are train_all's, without augmentation."""
+        LearnerBatch. -> dict(train=[epoch, R, k], test=[epoch, R, k]): the loss of each step's forward pass before its update, and of the
+        updated weights on the held-out fold; kept in self.kfold_log, and handed epoch by epoch to `writer(e, dict(train=[R, k],
+        test=[R, k]))`. The model and the object's own device learner are not touched (the reference trains copies). batchSize is accepted
+        and ignored, as in train_all; the pairs are train_all's, without augmentation.
+        val = (gtTrajs [kv, tau, s], actionSeqs [kv, tau, a]): after the step of every epoch e with e % 10 == 0 (learner_base.py:186-188)
+        every copy is rolled along the held-out trajectories (validate_fold: one launch for all copies); the dict gains
+        val=[ceil(epoch / 10), R, k] and the writer's dict of those epochs `val` [R, k]. The epochs then run in calls of 1, 10, 10, ... steps;
+        train and test are the bits of a run without val."""
         if val is not None:
-            raise ValueError("k_fold_validation: trajectory validation of the fold models (val) is not supported")
+            self._check_val(val)
+        if self.rb.n < 1:
+            raise ValueError("k_fold_validation: the replay buffer holds no transitions")
         rates = np.atleast_1d(np.asarray(learningRate, np.float32)).ravel()
         data = self.rb_trans()
         X, y = self.model.prepare_training_data(data["obs"], data["next_obs"], data["act"])
@@ -157,27 +164,77 @@ class LearnerBase:
         w = self.model.get_weights()
         R, k = len(rates), len(folds)
         batch = LearnerBatch(dict(W=w[0::2], b=w[1::2]), R * k, device=self._device)
+        vals = []
         try:
             batch.set_data(X, y)
             for r in range(R):
                 for f, (tr, te) in enumerate(folds):
                     batch.set_split(r * k + f, tr, te)
-            loss_train, loss_test = batch.train(epoch, np.repeat(rates, k))
+            if val is None:
+                loss_train, loss_test = batch.train(epoch, np.repeat(rates, k))
+            else:
+                pieces, e = [], 0
+                while e < epoch:  # epoch e = 0, then 1..10, 11..20, ...: a validation behind every epoch that is a multiple of 10
+                    steps = 1 if e == 0 else min(10, epoch - e)
+                    pieces.append(batch.train(steps, np.repeat(rates, k)))
+                    e += steps
+                    if (e - 1) % 10 == 0:
+                        vals.append(self.validate_fold(batch, val).reshape(R, k))
+                loss_train, loss_test = (np.concatenate([p[i] for p in pieces]) for i in (0, 1))
         finally:
             batch.close()
         self.kfold_log = dict(train=loss_train.reshape(epoch, R, k), test=loss_test.reshape(epoch, R, k))
+        if val is not None:
+            self.kfold_log["val"] = np.stack(vals)
         if callable(writer):
             for e in range(epoch):
-                writer(e, dict(train=self.kfold_log["train"][e], test=self.kfold_log["test"][e]))
+                entry = dict(train=self.kfold_log["train"][e], test=self.kfold_log["test"][e])
+                if val is not None and e % 10 == 0:
+                    entry["val"] = self.kfold_log["val"][e // 10]
+                writer(e, entry)
         return self.kfold_log
 
-    def grid_search(self, learningRates, k=2, epoch=250, seed=0):
+    def _check_val(self, val):
+        """val = (gtTrajs [kv, tau, s], actionSeqs [kv, tau, a]) with tau >= 2 -> the two arrays; ValueError before any device"""
+        if not isinstance(val, (tuple, list)) or len(val) != 2:
+            raise ValueError("val is (gtTrajs [k, tau, s], actionSeqs [k, tau, a])")
+        gt, act = np.asarray(val[0]), np.asarray(val[1])
+        if gt.ndim != 3 or act.ndim != 3 or gt.shape[:2] != act.shape[:2] or gt.shape[2] != self.sDim or act.shape[2] != self.aDim \
+                or gt.shape[0] < 1 or gt.shape[1] < 2:
+            raise ValueError("val is (gtTrajs [k, tau, %d], actionSeqs [k, tau, %d]) with k >= 1, tau >= 2, not %s and %s"
+                             % (self.sDim, self.aDim, gt.shape, act.shape))
+        return gt, act
+
+    def validate_fold(self, batch, val, split=False, norm=False):
+        """The multi-step error of every member of `batch` (learner_base.py:211-216 calls validate on each fold's model): each member's
+        network, as this learner's model (its kind and normalisation), rolled tau - 1 steps from gtTrajs[:, 0] along actionSeqs, all
+        members in ONE launch (LearnerBatch.rollout) -> err [B] = sum of squared errors / (k tau s); the t = 0 term is zero and counts in
+        the mean, as in validate (learner_base.py:264-267). split: also errSplit [B, s]. norm: behind each, its twin in the network's
+        output units, sse / Ystd^2 (a model that normalises its last 6 outputs only, NNAUVModelSpeed: over those, as validate)."""
+        gt, act = self._check_val(val)
+        kv, tau, s = gt.shape
+        sse = batch.rollout(self.model, gt[:, 0], np.ascontiguousarray(np.swapaxes(act[:, :tau - 1], 0, 1)),
+                            gt=np.ascontiguousarray(np.swapaxes(gt, 0, 1)))["sse"]
+        errSplit = sse / float(kv * tau)
+        out = [errSplit.mean(axis=1)]
+        ystd = np.asarray(self.model.Ystd, np.float64).ravel()
+        errSplitNorm = errSplit[:, -len(ystd):] / ystd ** 2
+        if norm:
+            out.append(errSplitNorm.mean(axis=1))
+        if split:
+            out += [errSplit] + ([errSplitNorm] if norm else [])
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def grid_search(self, learningRates, k=2, epoch=250, seed=0, val=None, by="test"):
         """learner_base.py:129-216 without its TensorBoard writers and its sigma axis (augmented rows go into the pool by the caller's hand):
-        every rate x every fold in one k_fold_validation -> (best_rate, table); table[r] = the mean over the folds of the last epoch's
-        held-out loss, best_rate its argmin."""
+        every rate x every fold in one k_fold_validation -> (best_rate, table); by="test": table[r] = the mean over the folds of the last
+        epoch's held-out loss; by="val" (needs val, k_fold_validation's): of the last validation's trajectory error. best_rate is the
+        table's argmin."""
+        if by not in ("test", "val") or (by == "val" and val is None):
+            raise ValueError('grid_search: by is "test" or "val", and "val" needs val = (gtTrajs, actionSeqs)')
         rates = [float(r) for r in np.atleast_1d(learningRates).ravel()]
-        log = self.k_fold_validation(k=k, learningRate=rates, epoch=epoch, seed=seed)
-        table = log["test"][-1].astype(np.float64).mean(axis=1)
+        log = self.k_fold_validation(k=k, learningRate=rates, epoch=epoch, seed=seed, val=val)
+        table = log[by][-1].astype(np.float64).mean(axis=1)
         return rates[int(np.argmin(table))], table
 
     def augment_data(self, X, y, samples=5, sigma=0.001, seed=1):

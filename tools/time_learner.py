@@ -18,7 +18,16 @@ each train on all n rows, as
 The same clock, warm-up, alternation and medians; the figure is microseconds per Adam step OF THE WHOLE SET (all B learners advance one
 step). No held-out rows: the lone learners have no test pass to set against one. After the timing every batch member's weights are
 compared with a lone learner's (they made the same number of steps from the same start): the bits must be equal.
-    tools/time_learner.py --batch 10,100 [--ns 264,4096] [--reps R] [--steps S] [--out FILE]"""
+    tools/time_learner.py --batch 10,100 [--ns 264,4096] [--reps R] [--steps S] [--out FILE]
+With --batch B[,B...] --validate it times the trajectory validation of a batch instead (csrc/mppi_learner_rollout.hip): the NNAUVModel network
+[16, 32, 32, 32, 13], B members of different weights, n trajectories (--ns, default 16 and 256) of T = 50 steps, as
+  (g) batch: one LearnerBatch.rollout(model, x0, V, gt=G) — every member in ONE launch, the squared errors summed on the device;
+  (h) lone:  B lone handles that already hold the members' weights, each Handle.model_rollout(x0, V, costs=False) (T + 1 launches) and the
+             squared error of the returned trajectory summed on the host — the only way to these numbers without the batch's kernel.
+             Creating the B handles and pushing the members' weights into them is timed once, apart.
+The same clock, warm-up, alternation and medians; the figure is microseconds per validation of the whole set. Afterwards every member's
+trajectory is compared with its handle's: the bits must be equal.
+    tools/time_learner.py --batch 10,100 --validate [--ns 16,256] [--reps R] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -137,17 +146,83 @@ def time_batch(o):
             fh.write("\n".join(lines) + "\n")
 
 
+def time_validate(o):
+    import torch
+    import mppi_tf_amd as m
+    T, CALLS = 50, 10  # a sample of the clock is CALLS validations, each ending in its own synchronisation
+    head = ["tools/time_learner.py --batch --validate: %s, NNAUVModel [16,32,32,32,13], T = %d steps, reps %d of %d calls; medians of a host clock around calls that end" % (
+        torch.cuda.get_device_name(0), T, o.reps, CALLS),
+        "in a synchronisation; microseconds per validation of the whole set of B networks (min-max), alternating rounds; batch = one LearnerBatch.rollout",
+        "(1 launch, sse on the device), lone = B handles holding the members' weights, each model_rollout (T + 1 launches) + the sse on the host;",
+        "setup = creating those B handles with the members' weights, once, not part of `lone`"]
+    print("\n".join(head), flush=True)
+    lines = list(head)
+    norm = dict(xmean=np.zeros(16, F32), xstd=np.ones(16, F32), ymean=np.zeros(13, F32), ystd=np.ones(13, F32))
+    desc = dict(kind="nnauv", s_dim=13, a_dim=6, dt=0.1, **norm)
+    for n in o.ns:
+        rng = np.random.default_rng(n)
+        x0 = np.zeros((n, 13), F32)
+        x0[:, :3], x0[:, 6], x0[:, 7:] = rng.uniform(-1, 1, (n, 3)), 1.0, rng.uniform(-0.3, 0.3, (n, 6))
+        V = rng.standard_normal((T, n, 6)).astype(F32)
+        G = (np.broadcast_to(x0, (T + 1, n, 13)) + 0.05 * rng.standard_normal((T + 1, n, 13))).astype(F32)
+        for B in o.batch:
+            nets = [make_net(NARROW, seed) for seed in range(B)]
+            for net in nets:
+                net["W"][-1] *= F32(0.1)
+            batch = m.LearnerBatch(nets[0], B)
+            for i, net in enumerate(nets):
+                batch.set_weights(net, member=i)
+            t0 = time.perf_counter()
+            lone = [m.Handle(k=1, tau=1, s_dim=13, a_dim=6, dt=0.1, sigma=np.eye(6, dtype=F32), goal=np.zeros(13, F32), nnauv=dict(net, **norm)) for net in nets]
+            setup = (time.perf_counter() - t0) * 1e6
+            G64 = G.astype(np.float64)
+
+            def lone_all():
+                return np.stack([((h.model_rollout(x0, V, costs=False)[0].astype(np.float64) - G64) ** 2).sum(axis=(0, 1)) for h in lone])
+
+            runs = (("batch", lambda: batch.rollout(desc, x0, V, gt=G)["sse"]), ("lone", lone_all))
+            got = {k: f() for k, f in runs}  # warm-up of every shape
+            t = {k: [] for k, _ in runs}
+            for _ in range(o.reps):
+                for k, f in runs:
+                    t0 = time.perf_counter()
+                    for _ in range(CALLS):
+                        f()
+                    t[k].append((time.perf_counter() - t0) / CALLS * 1e6)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            X = batch.rollout(desc, x0, V, trajectories=True)["X"]
+            same = all(np.array_equal(X[i], lone[i].model_rollout(x0, V, costs=False)[0]) for i in range(B))
+            rel = float(np.max(np.abs(got["batch"] - got["lone"]) / got["lone"]))
+            line = ("n=%-4d B=%-4d batch %9.1f us (%.1f-%.1f)   lone %10.1f us (%.1f-%.1f)  = %6.2fx batch   per network: batch %.1f us, lone %.1f us   setup of the "
+                    "lone handles %.0f us   trajectories bit-equal: %s   sse batch vs host fp64: %.2g relative" % (
+                        n, B, med["batch"], min(t["batch"]), max(t["batch"]), med["lone"], min(t["lone"]), max(t["lone"]), med["lone"] / med["batch"],
+                        med["batch"] / B, med["lone"] / B, setup, same, rel))
+            print(line, flush=True)
+            lines.append(line)
+            batch.close()
+            for h in lone:
+                h.close()
+    if o.out:
+        os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
+        with open(o.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=lambda v: [int(x) for x in v.split(",")], help="B[,B...]: time a LearnerBatch of B members against B lone learners")
-    ap.add_argument("--ns", type=lambda v: [int(x) for x in v.split(",")], default=[264, 4096], help="rows of the pool, with --batch")
+    ap.add_argument("--ns", type=lambda v: [int(x) for x in v.split(",")], default=None, help="rows of the pool, with --batch (264,4096); trajectories, with --validate (16,256)")
+    ap.add_argument("--validate", action="store_true", help="with --batch: time LearnerBatch.rollout against B lone handles' model_rollout")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--out", help="also write the table to this file")
     ap.add_argument("--dry-run", action="store_true", help="build the networks and the data, count the operations, time nothing (no GPU)")
     o = ap.parse_args()
+    if o.validate and not o.batch:
+        ap.error("--validate goes with --batch")
+    o.ns = o.ns or ([16, 256] if o.validate else [264, 4096])
     if o.batch and not o.dry_run:
-        return time_batch(o)
+        return time_validate(o) if o.validate else time_batch(o)
     if o.dry_run:
         for n in NS:
             X, Y = make_data(WIDE, n)

@@ -22,7 +22,12 @@ and the rate with the smallest mean held-out loss trains the model; one more lin
     python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2 --kfold-val
 chooses the rate by what the controller needs instead: every fold's network is rolled H steps open-loop along the windows of the round's
 episode (LearnerBase.validate_fold: all rates x folds in one launch) and the rate with the smallest mean H-step error wins; a second
-line per round shows that table."""
+line per round shows that table.
+    python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2 --kfold-episode
+chooses the rate by what the model is FOR: every fold's network becomes the model of its own controller — rates x folds learned
+controllers in one batch (BatchHandle.learned, one network per member, stepped in the same two launches as one) — and each runs a short
+closed-loop episode on the Fossen plant from x0 (LearnerBase.episode_fold: --episode-steps steps, all members in one call); the rate with
+the smallest mean summed state cost wins, and a second line per round shows that table."""
 import argparse
 import os
 import sys
@@ -93,6 +98,10 @@ def run(o):
                           auv=auv_task(1)["auv"])  # the plant: a handle that runs no rollouts, only its model is used
     learner = m.LearnerBase(model, bufferSize=o.rounds * o.steps)
     episodes, figures = [], []
+    by_episode = getattr(o, "kfold_episode", False)
+    # rates x folds learned controllers, one network each: they share the task and the Philox key, so only the networks tell them apart
+    folds_ctl = m.BatchHandle.learned(len(o.lrs) * o.kfold, model.mlp(), "nnauv", k=o.samples, seeds=[task["seed"]] * (len(o.lrs) * o.kfold),
+                                      **{k: v for k, v in task.items() if k not in ("s_dim", "a_dim", "seed")}) if by_episode else None
     for r in range(o.rounds):
         X, U, Cs = cont.run_episode(x0, o.steps, plant=fossen)
         episodes.append((X, U, Cs))
@@ -104,8 +113,9 @@ def run(o):
         if getattr(o, "kfold", 0):
             # the round's rate by k-fold cross-validation over --lrs: every rate x every fold trains at once, as one batch of learners
             by_val = getattr(o, "kfold_val", False)
+            episode = dict(controller=folds_ctl, plant=fossen, x0=x0, n_steps=o.episode_steps) if by_episode else None
             lr, table = learner.grid_search(o.lrs, k=o.kfold, epoch=o.epochs, val=windows_val(X, U, o.horizon) if by_val else None,
-                                            by="val" if by_val else "test")
+                                            by="episode" if by_episode else "val" if by_val else "test", episode=episode)
             held_out = learner.kfold_log["test"][-1].astype(np.float64).mean(axis=1)
             print("round %d: %d-fold held-out loss after %d epochs by learning rate: %s -> lr %g" % (
                 r + 1, o.kfold, o.epochs, ", ".join("%g: %.6g" % (a, b) for a, b in zip(o.lrs, held_out)), lr), flush=True)
@@ -113,6 +123,10 @@ def run(o):
                 print("round %d: %d-fold H-step open-loop squared error (H = %d, %d windows) after %d epochs by learning rate: %s -> lr %g" % (
                     r + 1, o.kfold, o.horizon, windows, 10 * ((o.epochs - 1) // 10) + 1,
                     ", ".join("%g: %.6g" % (a, b) for a, b in zip(o.lrs, table)), lr), flush=True)
+            if by_episode:
+                print("round %d: %d-fold summed state cost of a %d-step closed-loop episode on the plant after %d epochs by learning rate: %s "
+                      "-> lr %g" % (r + 1, o.kfold, o.episode_steps, o.epochs, ", ".join("%g: %.6g" % (a, b) for a, b in zip(o.lrs, table)), lr),
+                      flush=True)
         first, last = learner.train_all(learningRate=lr, epoch=o.epochs)
         cont.set_mlp(model.mlp())
         after = one_step_error(model, X, U)
@@ -124,6 +138,8 @@ def run(o):
                   r + 1, o.steps, figures[-1][0], before, after, learner.rb.n, o.epochs, first, last, o.horizon, h_text), flush=True)
         if getattr(o, "on_round", None) is not None:
             o.on_round(r, cont, model, X, U)
+    if folds_ctl is not None:
+        folds_ctl.close()
     cont.close()
     fossen.close()
     return learner, episodes, figures
@@ -145,7 +161,11 @@ def main(argv=None, on_round=None):
     ap.add_argument("--kfold", type=int, default=0, help="K >= 2: choose each round's learning rate among --lrs by K-fold cross-validation (LearnerBase.grid_search)")
     ap.add_argument("--lrs", type=lambda v: [float(x) for x in v.split(",")], default=None, help="a,b,c: the learning rates --kfold chooses from")
     ap.add_argument("--kfold-val", action="store_true", help="with --kfold: choose the rate by the folds' H-step open-loop error on the round's episode (LearnerBase.validate_fold)")
+    ap.add_argument("--kfold-episode", action="store_true", help="with --kfold (--model auv): choose the rate by a short closed-loop episode of every fold's network on the plant (LearnerBase.episode_fold)")
+    ap.add_argument("--episode-steps", type=int, default=10, help="steps of the --kfold-episode episodes")
     o = ap.parse_args(argv)
+    if o.kfold_episode and (not o.kfold or o.kfold_val or o.model != "auv" or o.episode_steps < 1):
+        ap.error("--kfold-episode goes with --kfold and --model auv, not with --kfold-val, and needs --episode-steps >= 1")
     if o.kfold_val and (not o.kfold or o.steps < o.horizon):
         ap.error("--kfold-val goes with --kfold and needs --steps >= --horizon")
     if bool(o.kfold) != bool(o.lrs):

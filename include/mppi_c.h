@@ -35,7 +35,8 @@ extern "C" {
 
 #define MPPI_ABI_VERSION 5 /* 5: MPPI_TUNE_FUSED_STEP / _ARMED_US / _ARMED_ALWAYS / _PRELAUNCH (no entry point changed), mppi_run_episode / mppi_batch_run_episode
                               (added; no entry point changed), mppi_learner_gradients and the [in, 256, 256, out] learner (added; no entry point changed),
-                              mppi_learner_batch_* (added; no entry point changed); 4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
+                              mppi_learner_batch_* (added; no entry point changed), mppi_create_batch_learned / mppi_batch_set_mlp (added; no entry point changed);
+                              4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
                               _load / _peek, MPPI_TUNE_TRACE (roctx ranges); mppi_set_mlp orders against the last step's stream;
                               3: the 13-state AUV family (MPPI_MODEL_AUV / _NN_AUV, mppi_auv_desc), StaticQuatCost / ElipseCost3D state costs,
                               mppi_auv_pieces, the learner (mppi_learner_*); 2: state_cost_kind / ellipse, transition log, tuning */
@@ -452,6 +453,37 @@ mppi_status mppi_batch_set_action_sequences(mppi_handle *h, const float *U, int 
 /* mppi_debug_get of ONE member (MPPI_DBG_*, the sizes of a lone handle) with the member's own constants: MPPI_DBG_WEIGHTS at its lambda,
  * MPPI_DBG_NOISE regenerated from its Philox key and sigma */
 mppi_status mppi_batch_debug_get(mppi_handle *h, int member, int what, float *out, size_t n);
+
+/* ---- batched learned-model controllers: one network per member --------------------------------------------------------------------
+ * B controllers of the learned 13-state models (MPPI_MODEL_NN_AUV, MPPI_MODEL_NN_AUV_SPEED; s_dim 13, a_dim 6), member m with its OWN
+ * network and normalisation cfgs[m].mlp, stepped in the same two launches as one. An entry point of its own, not a lifted refusal:
+ * mppi_create_batch and mppi_create_batch_configs keep refusing the learned kinds word for word, because the learned batch has another
+ * contract than theirs. Member m is bit for bit the lone handle mppi_create(&cfgs[m]) running the lane-per-rollout kernel
+ * k_rollout_gen<MODEL, HID, DIAG> - that handle's default for NNAUVModel with Dense(16) layers, otherwise the handle tuned with
+ * MPPI_TUNE_MLP32_VALU = 1 - fed the same x, goal and sequence on the same step counter: sample costs, beta, eta, U' and u. Against a lone
+ * handle on its DEFAULT matrix-core pipeline (k_rollout_nnauv_pc, k_rollout_nnspeed_pc) a member agrees as those kernels agree with the
+ * lane-per-rollout kernel: to rounding, inside the bars those kernels are tested to against fp64, not bit for bit. Members never
+ * interact.
+ *   per member: what mppi_create_batch_configs takes per member, and the network's weights and normalisation;
+ *   shared (else MPPI_ERR_INVALID_ARG naming the field): what mppi_create_batch_configs shares, and the network's shape (mlp.n_layers,
+ *     mlp.widths): 1-3 equal hidden layers of 16 or 32.
+ * Serves every state cost a lone learned 13-state handle holds (quadratic with a diagonal or dense Q, StaticQuatCost, ElipseCost3D; the
+ * quat_Q / ellipse3d parameters are shared), either action-cost form, sigma diagonal for all or dense for all, action limits, at most
+ * 1024 tiles (k = 65536) per member. The handle is an ordinary batched handle: mppi_batch_next / _next_device / _set_goals /
+ * _get/_set_action_sequences / _debug_get / _run_episode / _run_episode_plant, mppi_get/set_step_counter, mppi_set_action_limits,
+ * mppi_synchronize, mppi_profile_begin/end, mppi_rollout_kernel_name ("mppi::k_rollout_nn_batch<1, 32, true>") and mppi_destroy serve it.
+ * mppi_batch_run_episode steps member m's state with member m's own network.
+ * MPPI_ERR_UNSUPPORTED, before anything is allocated: MPPI_MODEL_MLP (the learned point mass is not batched), MPPI_MODEL_POINT_MASS and
+ * MPPI_MODEL_AUV (mppi_create_batch_configs serves them), normalize_cost, MPPI_FLAG_MLP_BF16X3, MPPI_FLAG_FP_CONTRACT, shard_count > 1,
+ * more than 1024 tiles per member; on the handle what any batch refuses. MPPI_ERR_INVALID_ARG: NULL cfgs / out, n < 1, a member without
+ * cfg.mlp, n * k too large. */
+/* n members, member m from cfgs[m]: what mppi_create_batch_configs takes per member (seed, goal, lambda, gamma, upsilon, sigma, Q)
+ * AND its own network cfgs[m].mlp (weights and normalisation; the descs may all be the same pointer). */
+mppi_status mppi_create_batch_learned(const mppi_config *cfgs, int n, mppi_handle **out);
+/* mppi_set_mlp for ONE member (member = -1: every member gets this network): same layer widths as at creation (else, and for a member
+ * out of range, MPPI_ERR_INVALID_ARG and nothing changes); orders against the streams as mppi_set_mlp does; takes effect with the next
+ * step. */
+mppi_status mppi_batch_set_mlp(mppi_handle *h, int member, const mppi_mlp_desc *mlp);
 
 /* ---- closed-loop episodes: n_steps control steps on the device, the handle's own model as the plant ---------------------------------
  * For t = 0 .. n_steps-1, per member:

@@ -139,6 +139,9 @@ SIGNATURES = {
     "mppi_batch_get_action_sequences": (C.c_int, [_H, FP, C.c_int]),
     "mppi_batch_set_action_sequences": (C.c_int, [_H, FP, C.c_int]),
     "mppi_batch_debug_get": (C.c_int, [_H, C.c_int, C.c_int, FP, C.c_size_t]),
+    # ... of the learned 13-state models, one network per member (BatchHandle.learned, BatchHandle.set_mlp)
+    "mppi_create_batch_learned": (C.c_int, [C.POINTER(Config), C.c_int, C.POINTER(_H)]),
+    "mppi_batch_set_mlp": (C.c_int, [_H, C.c_int, C.POINTER(MlpDesc)]),
     # closed-loop episodes on the device (Handle.run_episode, BatchHandle.run_episode)
     "mppi_run_episode": (C.c_int, [_H, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
     "mppi_batch_run_episode": (C.c_int, [_H, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
@@ -793,6 +796,64 @@ class BatchHandle(_HandleBase):
             self.set_tuning(key, val)
         if goals is not None:
             self.set_goals(goals)
+
+    _LEARNED = {"nnauv": (MODEL_NN_AUV, 16, 13), "nnauv_speed": (MODEL_NN_AUV_SPEED, 15, 6)}  # kind, network inputs, outputs
+
+    @classmethod
+    def learned(cls, n, nets, model="nnauv", *, k, tau, goals=None, tuning=None, normalize_cost=False, shard_count=1, mlp_bf16x3=False,
+                fp_contract=False, **cfg):
+        """mppi_create_batch_learned: n controllers of a learned 13-state model ("nnauv": NNAUVModel, "nnauv_speed": NNAUVModelSpeed), member m
+        with its OWN network. nets: one dict in the `nnauv=` format of Handle (every member gets it) or n of them, all of one shape;
+        k, tau and the other keywords as batch_configs' (seeds, goal, lam(s), gamma(s), upsilon(s), sigma(s), Q(s), quat_cost, ellipse3d, ...).
+        Member m is bit for bit the lone Handle of its config and network on k_rollout_gen (include/mppi_c.h)."""
+        if model not in cls._LEARNED:
+            raise ValueError('model must be "nnauv" or "nnauv_speed", not %r' % (model,))
+        kind, n_in, n_out = cls._LEARNED[model]
+        nets = [nets] * n if isinstance(nets, dict) else list(nets)
+        if len(nets) != n:
+            raise MppiError(ERR_INVALID_ARG, "nets must hold n = %d networks (or be one dict), not %d" % (n, len(nets)))
+        self = cls.__new__(cls)
+        lib = self.lib = load()
+        self.h = _H()
+        self.n, self.k, self.tau, self.s, self.a = n, k, tau, 13, 6
+        self._mlp_io = (n_in, n_out)
+        cfgs, keep = batch_configs(n, k, tau, 13, 6, **cfg)
+        for m in range(n):
+            cfgs[m].model_kind = kind
+            cfgs[m].normalize_cost, cfgs[m].shard_count = int(bool(normalize_cost)), shard_count
+            cfgs[m].flags |= (2 if mlp_bf16x3 else 0) | (4 if fp_contract else 0)
+            if nets[m] is not None:
+                desc, held = _mlp_desc(nets[m], n_in, n_out)
+                keep += held
+                cfgs[m].mlp = C.pointer(desc)
+        st = lib.mppi_create_batch_learned(cfgs, int(n), C.byref(self.h))
+        if st != OK:
+            self.h = _H()
+            self._check(st, None)
+        self.k_local = lib.mppi_local_samples(self.h)
+        for key, val in (tuning or {}).items():
+            self.set_tuning(key, val)
+        if goals is not None:
+            self.set_goals(goals)
+        return self
+
+    def set_mlp(self, member, net):
+        """mppi_batch_set_mlp: member's network <- net (member = -1: every member's); the shape is fixed at creation"""
+        if getattr(self, "_mlp_io", None) is None:
+            raise MppiError(ERR_INVALID_ARG, "not a batch of learned controllers (BatchHandle.learned)")
+        desc, held = _mlp_desc(net, *self._mlp_io)
+        self._check(self.lib.mppi_batch_set_mlp(self.h, int(member), C.byref(desc)))
+        del held
+
+    def load_learners(self, batch, model):
+        """Every member's weights of the LearnerBatch `batch` (as many members as this handle), with the normalisation of `model`
+        (LearnerBatch.model_desc: a model object or a dict with xmean, xstd, ymean, ystd), into the controllers, through the host."""
+        if batch.B != self.n:
+            raise MppiError(ERR_INVALID_ARG, "load_learners: the learner batch has %d members, the controllers %d" % (batch.B, self.n))
+        d = LearnerBatch.model_desc(model)
+        norm = {key: d.get(key) for key in ("xmean", "xstd", "ymean", "ystd")}
+        for m in range(self.n):
+            self.set_mlp(m, dict(batch.get_weights(m), **norm))
 
     def set_goals(self, goals):
         g = f32(goals).ravel()

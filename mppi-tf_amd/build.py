@@ -24,13 +24,14 @@ MLP_FLAGS = ["-fno-slp-vectorize"]
 # register on either side of every layer of k_rollout_mlp32_bx3 / k_rollout_nnauv32_bx3 (the asm MFMAs of the other kernels name their registers themselves)
 MLP_ONLY_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # the 13-state units, compiled with the MLP units' flags (the batched AUV step is the same kernel text as the gen unit's)
-MLP_STEMS = ("gen", "batch_gen")
+MLP_STEMS = ("gen", "batch_gen", "batch_nn")
 UNITS = ([("mppi_launch_mlp.hip", ["MPPI_UNIT_A=%d" % a], "mlp_a%d" % a) for a in (3, 2, 1, 4)]
          + [("mppi_launch_pc.hip", ["MPPI_UNIT_A=%d" % a], "pc_a%d" % a) for a in (4, 3, 2, 1)]
          + [("mppi_launch_batch.hip", ["MPPI_UNIT_A=%d" % a], "batch_a%d" % a) for a in (4, 3, 2, 1)]
          + [("mppi_launch_step.hip", ["MPPI_UNIT_A=%d" % a], "step_a%d" % a) for a in (4, 3, 2, 1)]
          + [("mppi_launch_tile.hip", ["MPPI_UNIT_A=%d" % a], "tile_a%d" % a) for a in (4, 3, 2, 1)]
-         + [("mppi_launch_gen.hip", [], "gen"), ("mppi_launch_batch_gen.hip", [], "batch_gen"), ("mppi_learner.hip", [], "learner"), ("mppi_learner_wide.hip", [], "learner_wide"),
+         + [("mppi_launch_gen.hip", [], "gen"), ("mppi_launch_batch_gen.hip", [], "batch_gen"), ("mppi_launch_batch_nn.hip", [], "batch_nn"),
+            ("mppi_learner.hip", [], "learner"), ("mppi_learner_wide.hip", [], "learner_wide"),
             ("mppi_learner_batch.hip", [], "learner_batch"), ("mppi_learner_rollout.hip", [], "learner_rollout"),
             ("mppi_capi.hip", [], "capi"), ("mppi_capi_set.hip", [], "capi_set"), ("mppi_capi_step.hip", [], "capi_step"),
             ("mppi_capi_shard.hip", [], "capi_shard"), ("mppi_capi_log.hip", [], "capi_log"), ("mppi_capi_debug.hip", [], "capi_debug"),
@@ -39,7 +40,7 @@ UNITS = ([("mppi_launch_mlp.hip", ["MPPI_UNIT_A=%d" % a], "mlp_a%d" % a) for a i
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mppi_device.hip.h", "mppi_ablate.hip.h", "mppi_kernels.hip.h", "mppi_mlp2.hip.h", "mppi_mlp_small.hip.h", "mppi_mlp32.hip.h",
            "mppi_handle.hip.h", "mppi_capi.hip.h", "mppi_step.hip.h", "mppi_gen.hip.h", "mppi_mfma32.hip.h", "mppi_bx3.hip.h", "mppi_mlp32b.hip.h", "mppi_rollout_pc.inc",
-           "mppi_rollout_auv_pc.inc", "mppi_episode_plant.hip.h", "mppi_model_rollout.hip.h", "mppi_learner.hip.h"]
+           "mppi_rollout_auv_pc.inc", "mppi_episode_plant.hip.h", "mppi_model_rollout.hip.h", "mppi_learner.hip.h", "mppi_nn_batch.hip.h"]
 ARCH = "gfx950"
 
 

@@ -132,6 +132,7 @@ extern "C" void mppi_destroy(mppi_handle *h)
     for (float *p : {h->d_bx, h->d_bu, h->d_ep, h->d_mr}) if (p) (void)hipFree(p);
     if (h->dM) (void)hipFree(h->dM);
     if (h->d_mlp_w) (void)hipFree(h->d_mlp_w);
+    if (h->d_nn_args) (void)hipFree(h->d_nn_args);
     if (h->dC) (void)hipFree(h->dC);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
     if (h->d_clip) (void)hipFree(h->d_clip);
@@ -148,13 +149,52 @@ extern "C" void mppi_destroy(mppi_handle *h)
 }
 
 // Upload a learned model's weights and normalisation (mppi_create: allocate = true; mppi_set_mlp: the same buffers again).
-static mppi_status upload_mlp(mppi_handle *h, const mppi_mlp_desc *d, bool allocate)
+// member >= 0 (a learned batch, mppi_create_batch_learned): member m's network in the same layout at d_mlp_w + m * nn_stride, its MlpDev at
+// dM + m and its padded layer pointers at d_nn_args + m (allocate: all B at once, with member 0); hm / small_args mirror member 0.
+static mppi_status upload_mlp(mppi_handle *h, const mppi_mlp_desc *d, bool allocate, int member = -1)
 {
     const int s = h->s, a = h->a;
     const bool speed = h->hc.model_kind == MPPI_MODEL_NN_AUV_SPEED;
     const bool nnauv = h->hc.model_kind == MPPI_MODEL_NN_AUV || speed;
     // NNAUVModel.prepare_data drops the position (nn_model.py:289-293); NNAUVModelSpeed's takes Euler angles, velocities, forces (:438-461)
     const int nin = speed ? 15 : (nnauv ? s + a - 3 : s + a), nout = speed ? 6 : s;
+    if (member >= 0) {
+        const size_t B = (size_t)h->batch;
+        if (allocate) {
+            size_t total = 0;
+            for (int l = 0, w_in = nin; l < d->n_layers; w_in = d->widths[l], ++l) total += (size_t)(w_in + 1) * (d->widths[l] + 1);
+            h->nn_stride = (total + 3) & ~(size_t)3; // members start 16-byte aligned
+            HIP_TRY(h, hipMalloc((void **)&h->d_mlp_w, sizeof(float) * h->nn_stride * B));
+            HIP_TRY(h, hipMalloc((void **)&h->dM, sizeof(MlpDev) * B));
+            HIP_TRY(h, hipMalloc((void **)&h->d_nn_args, sizeof(MlpSmallArgs) * B));
+        }
+        // the lone upload below into member m's block, on a scratch copy of the host mirrors
+        MlpDev hm{};
+        MlpSmallArgs sa{};
+        hm.n_layers = sa.n_layers = d->n_layers;
+        float *p = h->d_mlp_w + h->nn_stride * (size_t)member;
+        std::vector<float> image; // one member is ~12 KB: staged whole, one copy
+        for (int l = 0, w_in = nin; l < d->n_layers; w_in = d->widths[l], ++l) {
+            const int ld = (d->widths[l] & 1) ? d->widths[l] + 1 : d->widths[l];
+            const size_t nw = (size_t)w_in * ld, at = image.size();
+            image.resize(at + nw + ld, 0.0f);
+            for (int i = 0; i < w_in; ++i) for (int o = 0; o < d->widths[l]; ++o) image[at + (size_t)i * ld + o] = d->W[l][(size_t)i * d->widths[l] + o];
+            for (int o = 0; o < d->widths[l]; ++o) image[at + nw + o] = d->b[l][o];
+            hm.widths[l] = d->widths[l];
+            hm.ld[l] = ld;
+            hm.Wl[l] = sa.W[l] = p + at;
+            hm.bl[l] = sa.b[l] = p + at + nw;
+        }
+        for (int i = 0; i < kMaxS + kMaxA; ++i) { hm.xmean[i] = 0.f; hm.xstd[i] = 1.f; }
+        for (int i = 0; i < nin; ++i) { hm.xmean[i] = d->xmean ? d->xmean[i] : 0.f; hm.xstd[i] = d->xstd ? d->xstd[i] : 1.f; }
+        for (int i = 0; i < nout; ++i) { hm.ymean[i] = d->ymean ? d->ymean[i] : 0.f; hm.ystd[i] = d->ystd ? d->ystd[i] : 1.f; }
+        HIP_TRY(h, hipMemcpyAsync(p, image.data(), sizeof(float) * image.size(), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->dM + member, &hm, sizeof(MlpDev), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_nn_args + member, &sa, sizeof(MlpSmallArgs), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream)); // (the staging is pageable host memory of this call)
+        if (member == 0) { h->hm = hm; h->small_args = sa; }
+        return MPPI_OK;
+    }
     if (allocate) {
         size_t total = 0;
         for (int l = 0, w_in = nin; l < d->n_layers; w_in = d->widths[l], ++l) total += (size_t)(w_in + 1) * (d->widths[l] + 1);
@@ -449,7 +489,8 @@ static mppi_status allocate_handle(mppi_handle *h, const mppi_config *cfg, int B
     HIP_TRY(h, hipMalloc((void **)&h->d_part2, sizeof(float) * (size_t)nrec2 * (2 + h->HA)));
     HIP_TRY(h, hipMalloc((void **)&h->d_part3, sizeof(float) * (size_t)nrec3 * (2 + h->HA)));
     if (cfg->model_kind == MPPI_MODEL_MLP || cfg->model_kind == MPPI_MODEL_NN_AUV || cfg->model_kind == MPPI_MODEL_NN_AUV_SPEED) {
-        if (mppi_status st_ = upload_mlp(h, cfg->mlp, true); st_ != MPPI_OK) return st_;
+        // (a learned batch: member 0's network here, with the allocation for all; the creator uploads the others)
+        if (mppi_status st_ = upload_mlp(h, cfg->mlp, true, h->nn_batch ? 0 : -1); st_ != MPPI_OK) return st_;
     }
     HIP_TRY(h, hipMalloc((void **)&h->d_record, sizeof(float) * (2 + h->HA)));
     HIP_TRY(h, hipMalloc((void **)&h->d_dbg, sizeof(float) * 8 * B));
@@ -514,6 +555,7 @@ extern "C" mppi_status mppi_create(const mppi_config *cfg, mppi_handle **out)
 extern "C" mppi_status mppi_set_mlp(mppi_handle *h, const mppi_mlp_desc *d)
 {
     if (!h) return MPPI_ERR_INVALID_ARG;
+    if (h->nn_batch) return fail(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: a batched handle takes a member's network through mppi_batch_set_mlp");
     const int mk = h->hc.model_kind;
     if (mk != MPPI_MODEL_MLP && mk != MPPI_MODEL_NN_AUV && mk != MPPI_MODEL_NN_AUV_SPEED) return fail(h, MPPI_ERR_INVALID_ARG,
         "not a learned-model handle");
@@ -589,8 +631,14 @@ static bool same_auv(const mppi_auv_desc *x, const mppi_auv_desc *y)
 
 // The first field that every member must share in which b differs from a (NULL: none). What mppi_create derives the geometry, the model,
 // the cost's form and the kernel picks from is shared; seed, goal, lambda, gamma, upsilon, sigma and Q are each member's own.
-static const char *batch_shared_diff(const mppi_config *a, const mppi_config *b)
+// learned (mppi_create_batch_learned; every member has its cfg.mlp): also the network's shape, each member's weights being its own.
+static const char *batch_shared_diff(const mppi_config *a, const mppi_config *b, bool learned = false)
 {
+    if (learned) {
+        if (a->mlp->n_layers != b->mlp->n_layers) return "mlp.n_layers";
+        if (!a->mlp->widths || !b->mlp->widths) { if (a->mlp->widths != b->mlp->widths) return "mlp.widths"; }
+        else for (int l = 0; l < a->mlp->n_layers && l < kMlpSmallMaxLayers; ++l) if (a->mlp->widths[l] != b->mlp->widths[l]) return "mlp.widths";
+    }
     if (a->k != b->k) return "k";
     if (a->tau != b->tau) return "tau";
     if (!same_bits(a->dt, b->dt)) return "dt";
@@ -615,24 +663,54 @@ static const char *batch_shared_diff(const mppi_config *a, const mppi_config *b)
 // The batch of n members cfgs[0..n) (n >= 1): the handle mppi_create(&cfgs[0]) prepares, allocated for n members, member m's DevConsts
 // block filled from cfgs[m] exactly as a lone handle's. name_members: what mppi_create reports for cfgs[0] names member 0
 // (mppi_create_batch_configs); mppi_create_batch keeps the messages it always gave.
-static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_members, mppi_handle **out)
+// why cfg cannot be a member of a learned batch (mppi_create_batch_learned; NULL: it can, as far as the config alone tells)
+static const char *learned_batch_refusal(const mppi_config *cfg)
+{
+    switch (cfg->model_kind) {
+    case MPPI_MODEL_NN_AUV: case MPPI_MODEL_NN_AUV_SPEED: break;
+    case MPPI_MODEL_MLP: return "batched learned controllers: model MLP (the learned point mass) is not supported (NNAUVModel and "
+        "NNAUVModelSpeed only)";
+    case MPPI_MODEL_POINT_MASS: return "batched learned controllers: model POINT_MASS has no network: mppi_create_batch_configs serves it";
+    case MPPI_MODEL_AUV: return "batched learned controllers: model AUV has no network: mppi_create_batch_configs serves it";
+    default: return nullptr; // (mppi_create reports it)
+    }
+    if (cfg->normalize_cost) return "batched learned controllers: normalize_cost is not supported";
+    if (cfg->flags & MPPI_FLAG_MLP_BF16X3) return "batched learned controllers: MPPI_FLAG_MLP_BF16X3 is not supported";
+    if (cfg->flags & MPPI_FLAG_FP_CONTRACT) return "batched learned controllers: MPPI_FLAG_FP_CONTRACT is not supported";
+    if (cfg->shard_count > 1) return "batched learned controllers: sharding (shard_count > 1) is not supported";
+    return nullptr;
+}
+
+// learned: mppi_create_batch_learned's batch — the learned 13-state models, member m with its own network cfgs[m].mlp
+static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_members, mppi_handle **out, bool learned = false)
 {
     for (int m = 0; m < n; ++m)
         if (cfgs[m].struct_size != sizeof(mppi_config)) return fail(nullptr, MPPI_ERR_INVALID_ARG,
             "mppi_config.struct_size mismatch (use mppi_config_init)");
+    if (learned) {
+        if (const char *why = learned_batch_refusal(&cfgs[0])) return fail(nullptr, MPPI_ERR_UNSUPPORTED, why);
+        for (int m = 0; m < n; ++m) {
+            const mppi_mlp_desc *d = cfgs[m].mlp;
+            const std::string who = "batched learned controllers: member " + std::to_string(m) + ": ";
+            if (!d) return fail(nullptr, MPPI_ERR_INVALID_ARG, who + "cfg.mlp is NULL (every member brings its own network)");
+            if (!d->widths || !d->W || !d->b) return fail(nullptr, MPPI_ERR_INVALID_ARG, who + "cfg.mlp needs widths, W, b");
+            for (int l = 0; l < d->n_layers && l < kMlpSmallMaxLayers; ++l)
+                if (!d->W[l] || !d->b[l]) return fail(nullptr, MPPI_ERR_INVALID_ARG, who + "NULL MLP weight pointer");
+        }
+    }
     for (int m = 1; m < n; ++m)
-        if (const char *f = batch_shared_diff(&cfgs[0], &cfgs[m]))
+        if (const char *f = batch_shared_diff(&cfgs[0], &cfgs[m], learned))
             return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: cfgs[" + std::to_string(m) + "]." + f +
                 " differs from cfgs[0]." + f + " (every member shares it)");
     const mppi_config *cfg = &cfgs[0];
-    if (const char *why = batch_refusal(cfg)) return fail(nullptr, MPPI_ERR_UNSUPPORTED, why);
+    if (!learned) if (const char *why = batch_refusal(cfg)) return fail(nullptr, MPPI_ERR_UNSUPPORTED, why);
     mppi_handle *h = nullptr;
     if (mppi_status st = prepare_handle(cfg, name_members, &h); st != MPPI_OK) return st;
     auto refuse = [&](mppi_status st, const std::string &why) { mppi_destroy(h); return fail(nullptr, st, why); };
-    if (!h->is_gen && !pc_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED,
+    if (!learned && !h->is_gen && !pc_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED,
         "batched controllers: the producer/consumer rollout serves this shape only with s_dim = 2 a_dim, a_dim <= 4, tau <= 160 (<= 132 "
         "above 512 tiles)");
-    if (h->is_gen && !auv_batch_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED,
+    if (!learned && h->is_gen && !auv_batch_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED,
         "batched controllers: the Fossen AUV model is batched on its two-wave rollout (k_rollout_auv_pc) only");
     if (h->nbp > 1024) return refuse(MPPI_ERR_UNSUPPORTED,
         "batched controllers: at most 1024 tiles (k = 65536) per member (the finish combines a member's records in one pass)");
@@ -643,9 +721,39 @@ static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_member
     for (int m = 1; m < n; ++m)
         if (mppi_status st = member_consts(&cfgs[m], m, true, h, consts[m]); st != MPPI_OK) { mppi_destroy(h); return st; }
     h->batch = n;
+    h->nn_batch = learned ? 1 : 0;
     h->fuse_step = 0; // the two launches, always
-    if (mppi_status st = allocate_handle(h, cfg, n, consts.data()); st != MPPI_OK) { g_create_err = h->err; mppi_destroy(h); return st; }
+    mppi_status st = allocate_handle(h, cfg, n, consts.data());
+    for (int m = 1; learned && st == MPPI_OK && m < n; ++m) st = upload_mlp(h, cfgs[m].mlp, false, m);
+    if (st != MPPI_OK) { g_create_err = h->err; mppi_destroy(h); return st; }
     *out = h;
+    return MPPI_OK;
+}
+
+// ---- batched learned-model controllers (include/mppi_c.h; the kernel: mppi_nn_batch.hip.h) -------------------------------------------
+extern "C" mppi_status mppi_create_batch_learned(const mppi_config *cfgs, int n, mppi_handle **out)
+{
+    if (!cfgs || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfgs/out is NULL");
+    *out = nullptr;
+    if (n < 1) return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: n must be >= 1");
+    return create_batch(cfgs, n, true, out, true);
+}
+
+extern "C" mppi_status mppi_batch_set_mlp(mppi_handle *h, int member, const mppi_mlp_desc *d)
+{
+    MPPI_BATCH_ONLY(h);
+    if (!h->nn_batch) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp: not a batch of learned controllers (mppi_create_batch_learned)");
+    if (member < -1 || member >= h->batch) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp: member out of range");
+    if (!d || !d->widths || !d->W || !d->b) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp needs widths, W, b");
+    if (d->n_layers != h->hm.n_layers) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp: the layer count is fixed at creation");
+    for (int l = 0; l < d->n_layers; ++l) {
+        if (d->widths[l] != h->hm.widths[l]) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp: the layer widths are fixed at creation");
+        if (!d->W[l] || !d->b[l]) return fail(h, MPPI_ERR_INVALID_ARG, "NULL MLP weight pointer");
+    }
+    MPPI_ENTER(h);
+    HIP_TRY(h, hipDeviceSynchronize()); // steps in flight, on any stream, read the old weights (mppi_set_mlp)
+    for (int m = member < 0 ? 0 : member; m < (member < 0 ? h->batch : member + 1); ++m)
+        if (mppi_status st = upload_mlp(h, d, false, m); st != MPPI_OK) return st;
     return MPPI_OK;
 }
 

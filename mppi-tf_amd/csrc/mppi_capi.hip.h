@@ -169,6 +169,17 @@ inline bool auv_batch_eligible(const mppi_handle *h)
     return h->is_gen && h->hc.model_kind == MPPI_MODEL_AUV && !h->gen_one_wave && !h->normalize && h->shard_count == 1;
 }
 
+// a batch of learned 13-state controllers (mppi_create_batch_learned): what k_rollout_nn_batch runs
+inline bool nn_batch_eligible(const mppi_handle *h)
+{
+    return h->is_gen && h->nn_batch && h->d_nn_args != nullptr && !h->normalize && h->shard_count == 1 && !h->mlp_bx3;
+}
+// the batched step serves the handle (why not: batch_step's message)
+inline bool batch_eligible(const mppi_handle *h)
+{
+    return h->nn_batch ? nn_batch_eligible(h) : h->is_gen ? auv_batch_eligible(h) : pc_eligible(h);
+}
+
 // ---- host functions of mppi_capi_step.hip that other units call (comments at the definitions)
 hipError_t launch_tile(mppi_handle *h, const DevConsts *consts, hipStream_t st, int src, int mode, const float *x_dev, const float *U_dev,
                        const float *eps, float *cost, float *part, float *noise_out);

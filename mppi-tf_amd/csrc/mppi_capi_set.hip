@@ -59,7 +59,7 @@ extern "C" mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf,
     const mppi_unit_a *u = unit(h);
     const char *name = nullptr;
     switch (rollout_route(h, SRC_PHILOX, nullptr, true)) {
-    case ROUTE_BATCH: name = h->is_gen ? mppi_batch_auv_name(h) : u ? u->batch_name(h) : nullptr; break;
+    case ROUTE_BATCH: name = h->nn_batch ? mppi_batch_nn_name(h) : h->is_gen ? mppi_batch_auv_name(h) : u ? u->batch_name(h) : nullptr; break;
     case ROUTE_STEP: name = u ? u->step_name(h, STEP_FUSE) : nullptr; break;
     case ROUTE_PC: name = u ? u->pc_name(h, h->normalize ? PC_PASS_WEIGHTS : PC_PASS_PLAIN) : nullptr; break;
     case ROUTE_TILE: name = u ? u->tile_name(h, SRC_PHILOX, h->normalize ? MODE_COST_ONLY : MODE_ROLLOUT) : nullptr; break;

@@ -542,16 +542,22 @@ extern "C" mppi_status mppi_next_with_noise(mppi_handle *h, const float *x, int 
     return step_host(h, x, n_x, eps, n_eps, u_out, n_u);
 }
 
+// why the batched step does not serve the handle as it stands (batch_eligible)
+static const char *kBatchStepRefusal(const mppi_handle *h)
+{
+    return h->nn_batch ? "batched step: the learned 13-state models run on k_rollout_nn_batch only"
+         : h->is_gen   ? "batched step: the Fossen AUV model runs on k_rollout_auv_pc only"
+                       : "batched step: the horizon exceeds what this producer count serves (tau <= 132 with 3 producers)";
+}
+
 // rollouts of every member -> records, the finish of every member -> U', u_dev[B][a]; the sequences and the step counter advance
 static mppi_status batch_step(mppi_handle *h, hipStream_t st, const float *x_dev, float *u_dev)
 {
-    if (h->is_gen ? !auv_batch_eligible(h) : !pc_eligible(h))
-        return fail(h, MPPI_ERR_UNSUPPORTED, h->is_gen ? "batched step: the Fossen AUV model runs on k_rollout_auv_pc only"
-                                                       : "batched step: the horizon exceeds what this producer count serves (tau <= 132 "
-                                                           "with 3 producers)");
+    if (!batch_eligible(h)) return fail(h, MPPI_ERR_UNSUPPORTED, kBatchStepRefusal(h));
     TraceRange step_range(h, "mppi:batch_step");
     const ProfSlot p = prof_slot(h); // the dispatches' own begin / end
-    HIP_TRY(h, h->is_gen ? mppi_launch_batch_auv(h, st, p.rollout, x_dev) : per_a(h, &mppi_unit_a::batch, st, p.rollout, x_dev));
+    HIP_TRY(h, h->nn_batch ? mppi_launch_batch_nn(h, st, p.rollout, x_dev)
+             : h->is_gen ? mppi_launch_batch_auv(h, st, p.rollout, x_dev) : per_a(h, &mppi_unit_a::batch, st, p.rollout, x_dev));
     HIP_TRY(h, h->is_gen ? mppi_launch_batch_finish_auv(h, st, h->U_cur(), h->U_other(), u_dev, p.finish)
                          : per_a(h, &mppi_unit_a::batch_finish, st, (const float *)h->U_cur(), h->U_other(), u_dev, p.finish));
     if (p) prof_commit(h, st);
@@ -666,10 +672,7 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
     if (n_steps < 1 || n_steps > (1 << 24)) return fail(h, MPPI_ERR_INVALID_ARG, who + "n_steps must be in [1, 2^24]");
     if (h->shard_count != 1) return fail(h, MPPI_ERR_INVALID_ARG, "sharded handle: use mppi_shard_partial / mppi_shard_finish");
     if (!h->no_rollout.empty()) return fail(h, MPPI_ERR_UNSUPPORTED, h->no_rollout);
-    if (h->batch && (h->is_gen ? !auv_batch_eligible(h) : !pc_eligible(h)))
-        return fail(h, MPPI_ERR_UNSUPPORTED, h->is_gen ? "batched step: the Fossen AUV model runs on k_rollout_auv_pc only"
-                                                       : "batched step: the horizon exceeds what this producer count serves (tau <= 132 "
-                                                           "with 3 producers)");
+    if (h->batch && !batch_eligible(h)) return fail(h, MPPI_ERR_UNSUPPORTED, kBatchStepRefusal(h));
     EpisodePlant plant;
     if (with_plant)
         if (mppi_status st = check_plants(h, who, plants, n_plants, &plant); st != MPPI_OK) return st;
@@ -684,7 +687,8 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
     }
     const size_t n = (size_t)n_steps, xs = (size_t)B * s, us = (size_t)B * a;
     // k_mlp_step_ref: 2 * 256 floats per sample; k_nnauv_step_ref: 128. The handle's own model steps one sample, a learned plant B.
-    const size_t kScratch = 2 * kHid * (plant.learned ? (size_t)B : 1);
+    // ... and a learned batch as its own plant its B rows, row m through member m's network
+    const size_t kScratch = 2 * kHid * ((plant.learned || h->nn_batch) ? (size_t)B : 1);
     const size_t oX = 0, oU = oX + (n + 1) * xs, oC = oU + n * us, oG = oC + n * B, oW = oG + (goals ? n * xs : 0), oS = oW +
         (disturbance ? n * xs : 0);
     const size_t oP = (oS + kScratch + 1) & ~(size_t)1; // the plant table: B pointers, 8-byte aligned
@@ -723,7 +727,8 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
         if (learned && mk == MPPI_MODEL_MLP) {
             mlp_step_ref(stepper, st, x_t, B, u_t, B, scratch, x_next);
             HIP_TRY(h, hipGetLastError());
-        } else if (learned) HIP_TRY(h, mppi_gen_model_step(stepper, st, x_t, B, u_t, B, scratch, x_next));
+        } else if (learned && stepper == h && h->nn_batch) HIP_TRY(h, mppi_gen_model_step_members(h, st, x_t, u_t, B, scratch, x_next));
+        else if (learned) HIP_TRY(h, mppi_gen_model_step(stepper, st, x_t, B, u_t, B, scratch, x_next));
         const mppi_episode_tail e{x_t, u_t, dW ? dW + (size_t)t * xs : nullptr, (dG && t + 1 < n_steps) ? dG +
                                   (size_t)(t + 1) * xs : nullptr,
                                   dC + (size_t)t * B, x_next, learned ? 0 : 1};

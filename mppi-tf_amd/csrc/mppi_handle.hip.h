@@ -3,7 +3,7 @@
 // (creation), mppi_capi_set.hip (setters, accessors), mppi_capi_step.hip (the control step), mppi_capi_shard.hip, mppi_capi_log.hip,
 // mppi_capi_debug.hip — behind one internal header, mppi_capi.hip.h;
 // mppi_launch_tile.hip / _pc.hip / _mlp.hip / _batch.hip instantiate one kernel family each for ONE action dimension per object
-// (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step, mppi_episode.hip the plant of a closed-loop
+// (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step, mppi_launch_batch_nn.hip the batched step of the learned 13-state models, mppi_episode.hip the plant of a closed-loop
 // episode, mppi_episode_plant.hip the same with another handle's model as the plant, mppi_model_rollout.hip the open-loop rollout of the
 // handle's model (kernels and entry points). This header is what they share.
 #pragma once
@@ -133,6 +133,11 @@ struct mppi_handle {
     // the two batched launches (mppi_launch_batch.hip; the Fossen AUV model: mppi_launch_batch_gen.hip).
     int batch = 0;
     float *d_bx = nullptr, *d_bu = nullptr;
+    // a batch of learned 13-state controllers (mppi_create_batch_learned; mppi_launch_batch_nn.hip): member m's network is the lone upload
+    // layout at d_mlp_w + m * nn_stride, its MlpDev at dM + m, its padded layer pointers at d_nn_args + m (hm / small_args: member 0's)
+    int nn_batch = 0;
+    size_t nn_stride = 0; // floats
+    MlpSmallArgs *d_nn_args = nullptr;
     // a closed-loop episode's staging (mppi_run_episode / mppi_batch_run_episode): X | U | C | goals | disturbance | model-step scratch
     // [| the plants' constants pointers: mppi_run_episode_plant], one allocation that grows on demand
     float *d_ep = nullptr;
@@ -259,6 +264,12 @@ const void *mppi_gen_dev_consts(const mppi_handle *h); // the handle's GenConsts
 hipError_t mppi_launch_batch_auv(MPPI_BATCH_PARAMS);
 hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS);
 const char *mppi_batch_auv_name(const mppi_handle *h);
+// the batched step of the learned 13-state models, one network per member (mppi_launch_batch_nn.hip): every member's rollout in one launch
+// (k_rollout_nn_batch); the finish is mppi_launch_batch_finish_auv's
+hipError_t mppi_launch_batch_nn(MPPI_BATCH_PARAMS);
+const char *mppi_batch_nn_name(const mppi_handle *h);
+// mppi_gen_model_step with row i stepped by the network at dM + i (a learned batch as its own plant): x [k,13], v [k,6] -> next [k,13]
+hipError_t mppi_gen_model_step_members(mppi_handle *h, hipStream_t st, const float *x, const float *v, int k, float *scratch, float *out_next);
 // The plant of a closed-loop episode (mppi_episode.hip): ONE launch behind a control step serves every member. Member m: C[t] = the state
 // cost of x_t under the goal in force; x_{t+1} = model(x_t, u_t) (+ w_t) into the trajectory's next row, which is the next step's x_dev; the
 // goal of step t + 1 into the member's DevConsts.goal. model = 0 (a learned model): an existing model-step kernel has written x_next already.

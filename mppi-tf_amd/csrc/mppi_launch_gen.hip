@@ -238,10 +238,12 @@ hipError_t mppi_launch_gen(mppi_handle *h, const DevConsts *consts, hipStream_t 
 // NNAUVModel.build_step_graph in the reference's plain order (mul and add rounded separately, input index ascending, division by
 // Xstd): the slow evaluation behind mppi_model_step, like k_mlp_step_ref. Reads the UNPADDED weights through MlpDev.
 static __global__ void k_nnauv_step_ref(const DevConsts *__restrict__ C, const MlpDev *__restrict__ M, const float *__restrict__ x, int kx,
-                                        const float *__restrict__ v, int k, float *__restrict__ scratch, float *__restrict__ out_next, int speed)
+                                        const float *__restrict__ v, int k, float *__restrict__ scratch, float *__restrict__ out_next, int speed,
+                                        int member_stride)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= k) return;
+    M += (size_t)i * member_stride; // 0: one network for every row; 1: row i through the network of member i (a learned batch as its own plant)
     const int s = kGenS, a = kGenA, nin = speed ? kGenSpeedNin : kGenNin;
     float *cur = scratch + (size_t)i * 2 * 64, *nxt = cur + 64;
     const float *xi = x + (size_t)(kx == 1 ? 0 : i) * s;
@@ -304,7 +306,16 @@ hipError_t mppi_gen_model_step(mppi_handle *h, hipStream_t st, const float *x, i
     const dim3 grid((k + 63) / 64), block(64);
     if (h->hc.model_kind == MPPI_MODEL_AUV) hipLaunchKernelGGL(k_auv_step, grid, block, 0, st, (const GenConsts *)g->dG, x, kx, v, k, out_next);
     else hipLaunchKernelGGL(k_nnauv_step_ref, grid, block, 0, st, (const DevConsts *)h->dC, (const MlpDev *)h->dM, x, kx, v, k, scratch, out_next,
-                            h->hc.model_kind == MPPI_MODEL_NN_AUV_SPEED ? 1 : 0);
+                            h->hc.model_kind == MPPI_MODEL_NN_AUV_SPEED ? 1 : 0, 0);
+    return hipGetLastError();
+}
+
+// the same step with row i through member i's network (dM + i) of a learned batch: x [k,13], v [k,6], k = the member count
+hipError_t mppi_gen_model_step_members(mppi_handle *h, hipStream_t st, const float *x, const float *v, int k, float *scratch, float *out_next)
+{
+    if (!h->nn_batch || k != h->batch) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_nnauv_step_ref, dim3((k + 63) / 64), dim3(64), 0, st, (const DevConsts *)h->dC, (const MlpDev *)h->dM, x, k, v, k, scratch,
+                       out_next, h->hc.model_kind == MPPI_MODEL_NN_AUV_SPEED ? 1 : 0, 1);
     return hipGetLastError();
 }
 

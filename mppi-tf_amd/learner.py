@@ -142,7 +142,7 @@ class LearnerBase:
         X, y = self.model.prepare_training_data(data["obs"], data["next_obs"], data["act"])
         return self.train(X, y, epoch=epoch, learningRate=learningRate, val=val, writer=writer, augment=augment)
 
-    def k_fold_validation(self, k=10, learningRate=0.1, batchSize=32, epoch=100, val=None, writer=None, seed=0):
+    def k_fold_validation(self, k=10, learningRate=0.1, batchSize=32, epoch=100, val=None, writer=None, seed=0, episode=None):
         """learner_base.py:83-127: k copies of the model, copy f trained on every fold but f and tested on fold f after each step, each with
         its own Adam. learningRate: one rate, or R of them (R x k copies: grid_search's rate axis). All copies are members of ONE
         LearnerBatch. -> dict(train=[epoch, R, k], test=[epoch, R, k]): the loss of each step's forward pass before its update, and of the
@@ -181,9 +181,13 @@ class LearnerBase:
                     if (e - 1) % 10 == 0:
                         vals.append(self.validate_fold(batch, val).reshape(R, k))
                 loss_train, loss_test = (np.concatenate([p[i] for p in pieces]) for i in (0, 1))
+            # episode = episode_fold's keywords: every copy's closed-loop episode after the last epoch (grid_search by="episode")
+            ep_cost = None if episode is None else self.episode_fold(batch, **episode)
         finally:
             batch.close()
         self.kfold_log = dict(train=loss_train.reshape(epoch, R, k), test=loss_test.reshape(epoch, R, k))
+        if ep_cost is not None:
+            self.kfold_log["episode"] = ep_cost.reshape(1, R, k)
         if val is not None:
             self.kfold_log["val"] = np.stack(vals)
         if callable(writer):
@@ -225,15 +229,35 @@ class LearnerBase:
             out += [errSplit] + ([errSplitNorm] if norm else [])
         return out[0] if len(out) == 1 else tuple(out)
 
-    def grid_search(self, learningRates, k=2, epoch=250, seed=0, val=None, by="test"):
+    def episode_fold(self, batch, controller, plant, x0, n_steps, goals=None):
+        """What each member of `batch` is worth as a controller's model: every member's network, with this learner's model's normalisation,
+        goes into the B learned controllers `controller` (BatchHandle.learned of B = batch.B members; load_learners), which then run ONE
+        closed-loop episode of n_steps steps on the true vehicle `plant` (a Handle, or B of them) from x0 [s] or [B, s], from a zero sequence
+        and step counter 0 -> the summed state cost of each member's episode, C.sum(0), [B]. goals: [n_steps, s] or [n_steps, B, s]."""
+        B = batch.B
+        controller.load_learners(batch, self.model)
+        controller.set_action_sequences(np.zeros((B, controller.tau, controller.a), np.float32))
+        controller.set_step_counter(0)
+        x0 = np.asarray(x0, np.float32)
+        X0 = np.ascontiguousarray(np.broadcast_to(x0, (B, controller.s)))
+        if goals is not None:
+            goals = np.asarray(goals, np.float32)
+            goals = np.ascontiguousarray(np.broadcast_to(goals[:, None] if goals.ndim == 2 else goals, (int(n_steps), B, controller.s)))
+        return controller.run_episode(X0, n_steps, goals, plant=plant)[2].sum(0)
+
+    def grid_search(self, learningRates, k=2, epoch=250, seed=0, val=None, by="test", episode=None):
         """learner_base.py:129-216 without its TensorBoard writers and its sigma axis (augmented rows go into the pool by the caller's hand):
         every rate x every fold in one k_fold_validation -> (best_rate, table); by="test": table[r] = the mean over the folds of the last
-        epoch's held-out loss; by="val" (needs val, k_fold_validation's): of the last validation's trajectory error. best_rate is the
-        table's argmin."""
-        if by not in ("test", "val") or (by == "val" and val is None):
+        epoch's held-out loss; by="val" (needs val, k_fold_validation's): of the last validation's trajectory error; by="episode" (needs
+        episode = dict(controller=, plant=, x0=, n_steps=[, goals=]), episode_fold's arguments; the controller has R * k members): of the
+        summed state cost of each copy's closed-loop episode after the last epoch. best_rate is the table's argmin."""
+        if by == "episode":
+            if not isinstance(episode, dict) or not all(key in episode for key in ("controller", "plant", "x0", "n_steps")):
+                raise ValueError('grid_search: by="episode" needs episode = dict(controller=, plant=, x0=, n_steps=[, goals=])')
+        elif by not in ("test", "val") or (by == "val" and val is None):
             raise ValueError('grid_search: by is "test" or "val", and "val" needs val = (gtTrajs, actionSeqs)')
         rates = [float(r) for r in np.atleast_1d(learningRates).ravel()]
-        log = self.k_fold_validation(k=k, learningRate=rates, epoch=epoch, seed=seed, val=val)
+        log = self.k_fold_validation(k=k, learningRate=rates, epoch=epoch, seed=seed, val=val, episode=episode if by == "episode" else None)
         table = log[by][-1].astype(np.float64).mean(axis=1)
         return rates[int(np.argmin(table))], table
 

@@ -11,7 +11,12 @@ AUV at K=4096 H=40). In the sweep batch every member has its own lambda (log-spa
 to 2); the uniform batch shares the configuration. The two alternate as above. --only uniform times the uniform batch alone (through
 BatchHandle's shared keywords only, so the tool also runs on a package without per-member parameters).
     tools/time_batch.py [--model pm|auv] [--steps N] [--reps R] [--quick] [--only batch|streams|single] [--shape B,K,H] [--dry-run]
-    tools/time_batch.py --sweep [--only sweep|uniform] [--steps N] [--reps R] [--dry-run]"""
+    tools/time_batch.py --sweep [--only sweep|uniform] [--steps N] [--reps R] [--dry-run]
+--model nnauv|nnspeed [--hid 16|32 --layers 1..3]: the learned 13-state models with ONE NETWORK PER MEMBER (BatchHandle.learned) at K = 1024,
+H = 32, B in {8, 32, 128}: the batch; B lone DEFAULT handles stepped one after another on one stream (what a user does without the batch);
+the same B handles on B streams; and the batch's rollout kernel time (its own dispatch timestamps) with B distinct networks against B
+members sharing ONE network. --only batch|shared|serial|streams times one alone (a counter or kernel-trace run).
+    tools/time_batch.py --model nnauv|nnspeed [--hid 16|32] [--layers 1..3] [--shape B,K,H] [--only ...] [--steps N] [--reps R]"""
 import argparse
 import os
 import sys
@@ -98,6 +103,79 @@ def shape(B, K, H, a, steps, reps, only=None, model="pm"):
     return med
 
 
+def learned_net(model, hid, layers, seed):
+    """a random network of the learned 13-state model's shape with a normalisation (what the tests use)"""
+    rng = np.random.default_rng(seed)
+    dims = [16 if model == "nnauv" else 15] + [hid] * layers + [13 if model == "nnauv" else 6]
+    W = [(rng.uniform(-1, 1, (dims[i], dims[i + 1])) / np.sqrt(dims[i])).astype(np.float32) for i in range(layers + 1)]
+    b = [(rng.uniform(-1, 1, dims[i + 1]) / np.sqrt(dims[i])).astype(np.float32) for i in range(layers + 1)]
+    W[-1] *= 0.1
+    b[-1] *= 0.1
+    return dict(W=W, b=b, xmean=rng.uniform(-0.1, 0.1, dims[0]).astype(np.float32), xstd=rng.uniform(0.8, 1.2, dims[0]).astype(np.float32),
+                ymean=rng.uniform(-0.01, 0.01, dims[-1]).astype(np.float32), ystd=rng.uniform(0.8, 1.2, dims[-1]).astype(np.float32))
+
+
+def learned(B, K, H, model, hid, layers, steps, reps, only=None):
+    """one network per member: the batch (distinct networks / one shared network) against B lone default handles, serially and on B streams"""
+    kind = "nnauv" if model == "nnauv" else "nnauv_speed"
+    c = dict(k=K, tau=H, dt=0.1, lam=1.0, sigma=0.25 * np.eye(6), goal=[1.0, 2.0, -3.0, 0, 0, np.sin(0.2), np.cos(0.2)] + [0.0] * 6,
+             Q=np.array([10.0] * 3 + [5.0] * 4 + [1.0] * 6))
+    nets = [learned_net(model, hid, layers, 100 + i) for i in range(B)]
+    x0 = np.array([0.5, -0.5, 0.2, 0.0, 0.0, 0.0, 1.0, 0.3, 0.0, -0.1, 0.0, 0.05, 0.0], np.float32)
+    seeds = [1 + i for i in range(B)]
+    want = (lambda k: only in (None, k))
+    hb = m.BatchHandle.learned(B, nets, kind, seeds=seeds, **c) if want("batch") else None
+    hsh = m.BatchHandle.learned(B, nets[0], kind, seeds=seeds, **c) if want("shared") else None
+    hs = [m.Handle(seed=seeds[i], s_dim=13, a_dim=6, **{kind: nets[i]}, **c) for i in range(B)] if (want("serial") or want("streams")) else []
+    xb, ub = torch.from_numpy(np.tile(x0, (B, 1))).cuda(), torch.zeros((B, 6), device="cuda")
+    xs, us = [torch.from_numpy(x0.copy()).cuda() for _ in hs], [torch.zeros(6, device="cuda") for _ in hs]
+    one = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    names = dict(batch=hb.rollout_kernel_name() if hb else None, lone=hs[0].rollout_kernel_name() if hs else None)
+
+    def sync_all():
+        torch.cuda.synchronize()
+        for h in hs:
+            h.synchronize()
+
+    runs = {}
+    if hb:
+        runs["batch"] = (lambda: hb.next_device(xb.data_ptr(), ub.data_ptr(), None), hb.synchronize)
+    if hsh:
+        runs["shared"] = (lambda: hsh.next_device(xb.data_ptr(), ub.data_ptr(), None), hsh.synchronize)
+    if hs and want("serial"):
+        runs["serial"] = (lambda: [h.next_device(x.data_ptr(), u.data_ptr(), one) for h, x, u in zip(hs, xs, us)], one.synchronize)
+    if hs and want("streams"):
+        runs["streams"] = (lambda: [h.next_device(x.data_ptr(), u.data_ptr(), None) for h, x, u in zip(hs, xs, us)], sync_all)
+    for f, sy in runs.values():
+        clock(f, sy, max(20, steps // 4))
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, (f, sy) in runs.items():
+            t[k].append(clock(f, sy, steps) / steps)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    tag = "%s %dx%d B=%-3d K=%-5d H=%-3d" % (model, hid, layers, B, K, H)
+    what = dict(batch="batched step, B networks", shared="batched step, ONE network", serial="round of %d on one stream" % B,
+                streams="round of %d on %d streams" % (B, B))
+    for k in med:
+        print("%s  %-7s %9.2f us per %-28s (min %.2f, max %.2f over %d reps)  %8.2f us per controller step" % (
+            tag, k, med[k] * 1e6, what[k], min(t[k]) * 1e6, max(t[k]) * 1e6, reps, med[k] * 1e6 / B), flush=True)
+    if "batch" in med and "serial" in med:
+        print("%s  serial / batch = %.2f ; the slowest batch rep against the fastest serial rep: %.2f ; kernels %s | %s" % (
+            tag, med["serial"] / med["batch"], min(t["serial"]) / max(t["batch"]), names["batch"], names["lone"]), flush=True)
+    for k, h in (("batch", hb), ("shared", hsh)):  # the rollout kernel alone, from its dispatch's own begin / end
+        if h:
+            n = min(steps, 200)
+            h.profile_begin(n)
+            clock(runs[k][0], runs[k][1], n)
+            r, f, got = h.profile_end()
+            print("%s  %-7s rollout kernel %.2f us, finish %.2f us (mean of %d dispatches)" % (tag, k, r * 1e3, f * 1e3, got), flush=True)
+    for h in [hb, hsh] + hs:
+        if h:
+            h.close()
+    return med
+
+
 def sweep_kw(B, a_kw):
     """the per-member keywords of the sweep batch: lambda log-spaced over two decades, Sigma and Q scaled by 0.5 .. 2"""
     sc = np.linspace(0.5, 2.0, B)
@@ -153,15 +231,31 @@ def main():
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--quick", action="store_true", help="one shape only: B = 4, K = 4096, H = 64, a = 2")
-    ap.add_argument("--only", choices=("batch", "streams", "single", "sweep", "uniform"),
+    ap.add_argument("--only", choices=("batch", "streams", "single", "sweep", "uniform", "shared", "serial"),
                     help="time one of the three alone (--sweep: the sweep or the uniform batch alone)")
     ap.add_argument("--sweep", action="store_true", help="a per-member parameter sweep against the uniform batch of the same shape")
-    ap.add_argument("--model", choices=("pm", "auv"), default="pm", help="pm: the point mass; auv: the Fossen AUV at the reference's task")
+    ap.add_argument("--model", choices=("pm", "auv", "nnauv", "nnspeed"), default="pm",
+                    help="pm: the point mass; auv: the Fossen AUV at the reference's task; nnauv / nnspeed: the learned 13-state models, one network per member")
+    ap.add_argument("--hid", type=int, choices=(16, 32), default=32, help="nnauv / nnspeed: the hidden width")
+    ap.add_argument("--layers", type=int, choices=(1, 2, 3), default=3, help="nnauv / nnspeed: hidden layers")
     ap.add_argument("--shape", help="one shape only: B,K,H (the action dimension: 2 for pm, 6 for auv)")
     ap.add_argument("--dry-run", action="store_true", help="print the shapes and build their configurations, time nothing (no GPU)")
     o = ap.parse_args()
     if o.sweep:
         return main_sweep(o)
+    if o.model in ("nnauv", "nnspeed"):
+        shapes = [(B, 1024, 32) for B in (8, 32, 128)]
+        if o.shape:
+            shapes = [tuple(int(v) for v in o.shape.split(","))]
+        if o.dry_run:
+            for B, K, H in shapes:
+                print("%s %dx%d B=%-3d K=%-5d H=%-3d" % (o.model, o.hid, o.layers, B, K, H), flush=True)
+            return
+        print("tools/time_batch.py: %s, model %s %dx%d, steps %d, reps %d" % (torch.cuda.get_device_name(0), o.model, o.hid, o.layers, o.steps,
+                                                                           o.reps), flush=True)
+        for B, K, H in shapes:
+            learned(B, K, H, o.model, o.hid, o.layers, o.steps, o.reps, o.only)
+        return
     if o.model == "auv":
         shapes = ([(B, 4096, 40, 6) for B in (1, 2, 4, 8, 16)] + [(B, 16384, 40, 6) for B in (1, 2, 4, 8, 16)]
                   + [(B, 65536, 64, 6) for B in (1, 2)])

@@ -18,7 +18,8 @@ of the matrix-core rollout kernel, trained by the wide learner), the plant a k =
 state (x, vx, y, vy)); the H-step error takes the position components 0 and 2.
     python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2
 chooses each round's learning rate first: LearnerBase.grid_search trains every rate x every fold as ONE batch of learners (LearnerBatch)
-and the rate with the smallest mean held-out loss trains the model; one more line per round shows the table.
+and the rate with the smallest mean held-out loss trains the model; one more line per round shows the table. With --model point_mass
+--hidden 256 the batch is a WideLearnerBatch, the same held-out table for the [in, 256, 256, out] network.
     python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2 --kfold-val
 chooses the rate by what the controller needs instead: every fold's network is rolled H steps open-loop along the windows of the round's
 episode (LearnerBase.validate_fold: all rates x folds in one launch) and the rate with the smallest mean H-step error wins; a second
@@ -172,8 +173,8 @@ def main(argv=None, on_round=None):
         ap.error("--kfold K and --lrs a,b,c go together")
     if o.kfold and (o.kfold < 2 or o.kfold > o.steps):
         ap.error("--kfold: 2 <= K <= --steps")
-    if o.kfold and o.hidden == 256:
-        ap.error("--kfold trains a batch of narrow learners: not with --hidden 256")
+    if o.kfold_val and o.hidden == 256:
+        ap.error("--kfold-val rolls every fold's network: trajectory validation of wide members is not built, not with --hidden 256")
     if o.hidden == 256 and o.model != "point_mass":
         ap.error("--hidden 256 is the point-mass network: use --model point_mass")
     o.on_round = on_round

@@ -35,7 +35,8 @@ extern "C" {
 
 #define MPPI_ABI_VERSION 5 /* 5: MPPI_TUNE_FUSED_STEP / _ARMED_US / _ARMED_ALWAYS / _PRELAUNCH (no entry point changed), mppi_run_episode / mppi_batch_run_episode
                               (added; no entry point changed), mppi_learner_gradients and the [in, 256, 256, out] learner (added; no entry point changed),
-                              mppi_learner_batch_* (added; no entry point changed), mppi_create_batch_learned / mppi_batch_set_mlp (added; no entry point changed);
+                              mppi_learner_batch_* (added; no entry point changed), mppi_create_batch_learned / mppi_batch_set_mlp (added; no entry point changed),
+                              mppi_learner_wide_batch_* (added; no entry point changed);
                               4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
                               _load / _peek, MPPI_TUNE_TRACE (roctx ranges); mppi_set_mlp orders against the last step's stream;
                               3: the 13-state AUV family (MPPI_MODEL_AUV / _NN_AUV, mppi_auv_desc), StaticQuatCost / ElipseCost3D state costs,
@@ -678,6 +679,45 @@ mppi_status mppi_learner_batch_rollout(mppi_learner_batch *lb, const mppi_learne
                                        const float *x0 /* [kx, s], kx in {1, n} */, int kx, const float *V /* [T, n, a] */,
                                        const float *G /* [T+1, n, s] or NULL */, int n, int T,
                                        double *sse_out /* [B, s] or NULL; needs G */, float *X_out /* [B, T+1, n, s] or NULL */);
+
+/* ---- batched WIDE learners: B learners of the [in, 256, 256, out] network (the one mppi_learner_create accepts beside the narrow shapes,
+ * the network of an MPPI_MODEL_MLP controller) in the launches of one — mppi_learner_batch_* restated for that network, as an object of its
+ * own (mppi_learner_batch_create goes on refusing the shape). The entry points are the namesakes' with the object type exchanged.
+ * n_members 1..1024 (else MPPI_ERR_INVALID_ARG); n_layers = 3 and widths[4] exactly [1..32, 256, 256, 1..32], anything else is
+ * MPPI_ERR_UNSUPPORTED; both checked before the device is touched. Every member starts from the same W, b.
+ * Data: ONE pool X [n, in], Y [n, out] for all members (set_data; it resets every split). Member m trains on the rows
+ * train_idx[0..n_train) in that order and reports its held-out loss over test_idx[0..n_test) (set_split; indices may repeat, n_train >= 1,
+ * n_test >= 0; an index outside [0, n) is MPPI_ERR_INVALID_ARG and nothing changes). Before any set_split a member trains on rows 0..n-1
+ * and has no test rows.
+ * lr, beta1, beta2, eps per member ([B] arrays; NULL = 0.9 / 0.999 / 1e-7); one step counter serves the batch. loss_train[t * B + m] is
+ * the loss of step t's forward pass before its update; loss_test[t * B + m] is the loss of the weights AFTER step t's update on the
+ * member's test rows, NaN for a member without test rows. train enqueues every step on the object's own stream (nine launches per step
+ * for any B, twelve with test losses) and synchronises once; evaluate returns both losses of the current weights without an update.
+ * The contract: member m is bit-identical — weights, loss_train, loss_test — to a lone [in, 256, 256, out] mppi_learner created with the
+ * same weights, given mppi_learner_set_data(X[train_idx_m], Y[train_idx_m]) and trained with member m's rates from the same step count
+ * (its loss_test: mppi_learner_evaluate of a lone learner holding the member's weights on X[test_idx_m], Y[test_idx_m]). Members never
+ * interact. Deterministic (no float atomics). A member costs 1.0 MB of weights and moments, 0.33 MB of partial tiles per 512 training rows
+ * of the largest split and 4.4 KB of rows, activations and deltas per row of the largest split: a batch too large for the device is MPPI_ERR_ALLOC and the object stays destroyable (and usable
+ * after smaller splits). Not thread-safe per object. Errors as the learner's: mppi_learner_wide_batch_last_error(NULL) after a failed create.
+ * Out of scope: trajectory validation of a wide batch — mppi_learner_batch_rollout stays narrow-only and has no wide namesake. */
+typedef struct mppi_learner_wide_batch mppi_learner_wide_batch;
+mppi_status mppi_learner_wide_batch_create(int n_members, int n_layers /* 3 */, const int32_t *widths /* [4] */, const float *const *W,
+                                           const float *const *b, int device, mppi_learner_wide_batch **out);
+void mppi_learner_wide_batch_destroy(mppi_learner_wide_batch *wb);
+const char *mppi_learner_wide_batch_last_error(const mppi_learner_wide_batch *wb);
+int mppi_learner_wide_batch_size(const mppi_learner_wide_batch *wb);
+mppi_status mppi_learner_wide_batch_set_data(mppi_learner_wide_batch *wb, const float *X, const float *Y, int n); /* the shared pool */
+mppi_status mppi_learner_wide_batch_set_split(mppi_learner_wide_batch *wb, int member, const int32_t *train_idx, int n_train,
+                                              const int32_t *test_idx, int n_test);
+mppi_status mppi_learner_wide_batch_set_weights(mppi_learner_wide_batch *wb, int member /* -1: every member */, const float *const *W,
+                                                const float *const *b);
+mppi_status mppi_learner_wide_batch_get_weights(mppi_learner_wide_batch *wb, int member, float *const *W, float *const *b);
+mppi_status mppi_learner_wide_batch_reset_optimizer(mppi_learner_wide_batch *wb);
+mppi_status mppi_learner_wide_batch_get_step(mppi_learner_wide_batch *wb, int *step);
+mppi_status mppi_learner_wide_batch_train(mppi_learner_wide_batch *wb, int steps, const float *lr /* [B] */, const float *beta1,
+                                          const float *beta2, const float *eps /* each [B] or NULL = 0.9 / 0.999 / 1e-7 */,
+                                          float *loss_train /* [steps, B] or NULL */, float *loss_test /* [steps, B] or NULL */);
+mppi_status mppi_learner_wide_batch_evaluate(mppi_learner_wide_batch *wb, float *loss_train /* [B] */, float *loss_test /* [B] */);
 
 #ifdef __cplusplus
 }

@@ -182,6 +182,10 @@ SIGNATURES = {
     # ... their trajectory validation (LearnerBatch.rollout, LearnerBase.validate_fold)
     "mppi_learner_batch_rollout": (C.c_int, [_H, C.POINTER(LearnerModel), FP, C.c_int, FP, FP, C.c_int, C.c_int, DP, FP]),
 }
+# batched wide learners ([in, 256, 256, out]): the narrow batch's twelve signatures under another prefix
+SIGNATURES.update({"mppi_learner_wide_batch_" + e: SIGNATURES["mppi_learner_batch_" + e] for e in (
+    "create", "destroy", "last_error", "size", "set_data", "set_split", "set_weights", "get_weights", "reset_optimizer", "get_step", "train",
+    "evaluate")})
 
 _lib = None
 
@@ -1034,33 +1038,35 @@ class Learner:
         return int(v.value)
 
 
-class LearnerBatch:
-    """RAII wrapper of one mppi_learner_batch: n_members narrow learners (widths <= 32, 1-4 layers) that share one data pool and
-    step in the same launches (mppi_learner_batch.hip). Every member starts from `weights`, trains on its own rows of the pool
-    (set_split) with its own Adam rates, and is bit-identical to a lone Learner given those rows."""
+class _LearnerBatchBase:
+    """What LearnerBatch and WideLearnerBatch share: the two objects' entry points are namesakes with one signature each, _PREFIX apart."""
+    _PREFIX = None
+
+    def _f(self, name):
+        return getattr(self.lib, self._PREFIX + name)
 
     def __init__(self, weights, n_members, device=0):
-        lib = self.lib = load()
+        self.lib = load()
         self.Ws = [f32(w) for w in weights["W"]]
         self.bs = [f32(b).ravel() for b in weights["b"]]
         self.widths = [self.Ws[0].shape[0]] + [w.shape[1] for w in self.Ws]
         wd = (C.c_int32 * len(self.widths))(*self.widths)
         self.h = _H()
-        st = lib.mppi_learner_batch_create(int(n_members), len(self.Ws), wd, Learner._ptrs(self.Ws), Learner._ptrs(self.bs), device, C.byref(self.h))
+        st = self._f("create")(int(n_members), len(self.Ws), wd, Learner._ptrs(self.Ws), Learner._ptrs(self.bs), device, C.byref(self.h))
         if st != OK:
             self.h = _H()
-            raise MppiError(st, (lib.mppi_learner_batch_last_error(None) or b"").decode())
-        self.B = int(lib.mppi_learner_batch_size(self.h))
+            raise MppiError(st, (self._f("last_error")(None) or b"").decode())
+        self.B = int(self._f("size")(self.h))
         self.n = 0
 
     def _check(self, st):
         if st != OK:
-            raise MppiError(st, (self.lib.mppi_learner_batch_last_error(self.h) or b"").decode())
+            raise MppiError(st, (self._f("last_error")(self.h) or b"").decode())
 
     def close(self):
         h, self.h = getattr(self, "h", None), None
         if h:
-            self.lib.mppi_learner_batch_destroy(h)
+            self._f("destroy")(h)
 
     def __del__(self):
         try:
@@ -1072,7 +1078,7 @@ class LearnerBatch:
         """the pool every member draws its rows from; resets every split (train on all rows, no test rows)"""
         X, Y = f32(X, (-1, self.widths[0])), f32(Y, (-1, self.widths[-1]))
         assert X.shape[0] == Y.shape[0]
-        self._check(self.lib.mppi_learner_batch_set_data(self.h, fp(X), fp(Y), X.shape[0]))
+        self._check(self._f("set_data")(self.h, fp(X), fp(Y), X.shape[0]))
         self.n = X.shape[0]
 
     @staticmethod
@@ -1089,17 +1095,17 @@ class LearnerBatch:
         """member trains on pool rows train_idx (in that order, repeats allowed) and reports its held-out loss on test_idx"""
         tr, te = self._idx(train_idx), self._idx(test_idx)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None
-        self._check(self.lib.mppi_learner_batch_set_split(self.h, int(member), ip(tr), tr.size, ip(te), te.size))
+        self._check(self._f("set_split")(self.h, int(member), ip(tr), tr.size, ip(te), te.size))
 
     def set_weights(self, weights, member=-1):
         Ws, bs = [f32(w) for w in weights["W"]], [f32(b).ravel() for b in weights["b"]]
         if [w.shape for w in Ws] != [w.shape for w in self.Ws] or [b.shape for b in bs] != [b.shape for b in self.bs]:
             raise MppiError(ERR_INVALID_ARG, "weights of another shape than the batch's network")
-        self._check(self.lib.mppi_learner_batch_set_weights(self.h, int(member), Learner._ptrs(Ws), Learner._ptrs(bs)))
+        self._check(self._f("set_weights")(self.h, int(member), Learner._ptrs(Ws), Learner._ptrs(bs)))
 
     def get_weights(self, member):
         Ws, bs = [np.zeros_like(w) for w in self.Ws], [np.zeros_like(b) for b in self.bs]
-        self._check(self.lib.mppi_learner_batch_get_weights(self.h, int(member), Learner._ptrs(Ws), Learner._ptrs(bs)))
+        self._check(self._f("get_weights")(self.h, int(member), Learner._ptrs(Ws), Learner._ptrs(bs)))
         return dict(W=Ws, b=bs)
 
     def _per_member(self, v, name):
@@ -1121,25 +1127,39 @@ class LearnerBatch:
         if hp[0] is None:
             raise MppiError(ERR_INVALID_ARG, "lr is required")
         tr, te = np.zeros((max(steps, 0), self.B), np.float32), np.zeros((max(steps, 0), self.B), np.float32)
-        self._check(self.lib.mppi_learner_batch_train(self.h, steps, *[fp(a) for a in hp], fp(tr), fp(te)))
+        self._check(self._f("train")(self.h, steps, *[fp(a) for a in hp], fp(tr), fp(te)))
         return tr, te
 
     def evaluate(self):
         """(loss_train [B], loss_test [B]) of the current weights; no update"""
         tr, te = np.zeros(self.B, np.float32), np.zeros(self.B, np.float32)
-        self._check(self.lib.mppi_learner_batch_evaluate(self.h, fp(tr), fp(te)))
+        self._check(self._f("evaluate")(self.h, fp(tr), fp(te)))
         return tr, te
 
     def reset_optimizer(self):
-        self._check(self.lib.mppi_learner_batch_reset_optimizer(self.h))
+        self._check(self._f("reset_optimizer")(self.h))
 
     def step_count(self):
         v = C.c_int(0)
-        self._check(self.lib.mppi_learner_batch_get_step(self.h, C.byref(v)))
+        self._check(self._f("get_step")(self.h, C.byref(v)))
         return int(v.value)
 
+
+class WideLearnerBatch(_LearnerBatchBase):
+    """RAII wrapper of one mppi_learner_wide_batch: n_members learners of the [in, 256, 256, out] network (in, out <= 32) that share one
+    data pool and step in the same launches (mppi_learner_wide_batch.hip). LearnerBatch's methods and meaning, member for member
+    bit-identical to a lone wide Learner given the member's rows. It has no rollout: trajectory validation of wide members is not built."""
+    _PREFIX = "mppi_learner_wide_batch_"
+
+
+class LearnerBatch(_LearnerBatchBase):
+    """RAII wrapper of one mppi_learner_batch: n_members narrow learners (widths <= 32, 1-4 layers) that share one data pool and
+    step in the same launches (mppi_learner_batch.hip). Every member starts from `weights`, trains on its own rows of the pool
+    (set_split) with its own Adam rates, and is bit-identical to a lone Learner given those rows."""
+    _PREFIX = "mppi_learner_batch_"
+
     # ---- trajectory validation (mppi_learner_batch_rollout, include/mppi_c.h)
-    _KINDS = {"mlp": MODEL_MLP, "nnauv": MODEL_NN_AUV, "nnauv_speed": MODEL_NN_AUV_SPEED}
+    _KINDS ={"mlp": MODEL_MLP, "nnauv": MODEL_NN_AUV, "nnauv_speed": MODEL_NN_AUV_SPEED}
 
     @classmethod
     def model_desc(cls, model):

@@ -7,13 +7,15 @@ mean / std of the data, noise augmentation of the inputs) is numpy on the host, 
 The reference's replay buffer is cpprb's ReplayBuffer (a ring of transitions): restated here as three numpy arrays.
 k_fold_validation / grid_search (learner_base.py:83-216) train their k x R copies of the network as ONE LearnerBatch: every copy steps
 in the same launches (mppi_learner_batch.hip), and validate_fold rolls every copy along held-out trajectories in one more
-(mppi_learner_rollout.hip). TensorBoard logging and plotting are outside the path.
+(mppi_learner_rollout.hip). A model whose network is [in, 256, 256, out] trains its copies as ONE WideLearnerBatch
+(mppi_learner_wide_batch.hip) instead; trajectory validation of wide members is not built, so val= / episode= are refused for it.
+TensorBoard logging and plotting are outside the path.
 """
 import os
 
 import numpy as np
 
-from ._lib import Learner, LearnerBatch
+from ._lib import Learner, LearnerBatch, WideLearnerBatch
 
 
 def kfold_indices(n, k, seed=0):
@@ -157,13 +159,17 @@ class LearnerBase:
             self._check_val(val)
         if self.rb.n < 1:
             raise ValueError("k_fold_validation: the replay buffer holds no transitions")
+        w = self.model.get_weights()
+        wide = self._is_wide(w)
+        if wide and (val is not None or episode is not None):
+            raise ValueError("k_fold_validation: val= and episode= roll every member's network, and trajectory validation of wide members "
+                             "is not built ([in, 256, 256, out] trains and tests as a WideLearnerBatch; choose by=\"test\")")
         rates = np.atleast_1d(np.asarray(learningRate, np.float32)).ravel()
         data = self.rb_trans()
         X, y = self.model.prepare_training_data(data["obs"], data["next_obs"], data["act"])
         folds = kfold_indices(len(X), k, seed)
-        w = self.model.get_weights()
         R, k = len(rates), len(folds)
-        batch = LearnerBatch(dict(W=w[0::2], b=w[1::2]), R * k, device=self._device)
+        batch = (WideLearnerBatch if wide else LearnerBatch)(dict(W=w[0::2], b=w[1::2]), R * k, device=self._device)
         vals = []
         try:
             batch.set_data(X, y)
@@ -197,6 +203,12 @@ class LearnerBase:
                     entry["val"] = self.kfold_log["val"][e // 10]
                 writer(e, entry)
         return self.kfold_log
+
+    @staticmethod
+    def _is_wide(w):
+        """is [W0, b0, W1, b1, ...] the [in, 256, 256, out] network (in, out <= 32) that a WideLearnerBatch trains?"""
+        widths = [np.shape(w[0])[0]] + [np.shape(k)[1] for k in w[0::2]]
+        return len(widths) == 4 and widths[1] == widths[2] == 256 and 1 <= widths[0] <= 32 and 1 <= widths[3] <= 32
 
     def _check_val(self, val):
         """val = (gtTrajs [kv, tau, s], actionSeqs [kv, tau, a]) with tau >= 2 -> the two arrays; ValueError before any device"""

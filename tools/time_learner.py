@@ -19,6 +19,9 @@ The same clock, warm-up, alternation and medians; the figure is microseconds per
 step). No held-out rows: the lone learners have no test pass to set against one. After the timing every batch member's weights are
 compared with a lone learner's (they made the same number of steps from the same start): the bits must be equal.
     tools/time_learner.py --batch 10,100 [--ns 264,4096] [--reps R] [--steps S] [--out FILE]
+With --batch B[,B...] --wide the same table is taken for the [9, 256, 256, 6] network: (d) is one WideLearnerBatch of B members
+(csrc/mppi_learner_wide_batch.hip: 9 launches per step for all members), (e) and (f) are B lone wide Learners (9 B launches per step of the set).
+    tools/time_learner.py --batch 10,100 --wide [--ns 264,4096] [--reps R] [--steps S] [--out profiles/learner_wide_batch_time.txt]
 With --batch B[,B...] --validate it times the trajectory validation of a batch instead (csrc/mppi_learner_rollout.hip): the NNAUVModel network
 [16, 32, 32, 32, 13], B members of different weights, n trajectories (--ns, default 16 and 256) of T = 50 steps, as
   (g) batch: one LearnerBatch.rollout(model, x0, V, gt=G) — every member in ONE launch, the squared errors summed on the device;
@@ -89,17 +92,18 @@ def time_batch(o):
     import torch
     import mppi_tf_amd as m
     lr = 1e-3
-    head = ["tools/time_learner.py --batch: %s, [16,32,32,32,13], %d Adam steps per call, reps %d; medians of a host clock around calls that end in one" % (
-        torch.cuda.get_device_name(0), o.steps, o.reps),
+    dims, Batch, name = (WIDE, m.WideLearnerBatch, "WideLearnerBatch") if o.wide else (NARROW, m.LearnerBatch, "LearnerBatch")
+    head = ["tools/time_learner.py --batch%s: %s, [%s], %d Adam steps per call, reps %d; medians of a host clock around calls that end in one" % (
+        " --wide" if o.wide else "", torch.cuda.get_device_name(0), ",".join(str(d) for d in dims), o.steps, o.reps),
         "synchronisation each (every learner enqueues on its own stream); microseconds per Adam step of the whole set of B learners (min-max), alternating rounds;",
-        "batch = one LearnerBatch of B members, sequential = B lone Learners one after another, threads = the same B Learners from B host threads at once"]
+        "batch = one %s of B members, sequential = B lone Learners one after another, threads = the same B Learners from B host threads at once" % name]
     print("\n".join(head), flush=True)
     lines = list(head)
-    net = make_net(NARROW)
+    net = make_net(dims)
     for n in o.ns:
-        X, Y = make_data(NARROW, n)
+        X, Y = make_data(dims, n)
         for B in o.batch:
-            batch = m.LearnerBatch(net, B)
+            batch = Batch(net, B)
             batch.set_data(X, Y)
             lone = [m.Learner(net) for _ in range(B)]
             for l in lone:
@@ -212,6 +216,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=lambda v: [int(x) for x in v.split(",")], help="B[,B...]: time a LearnerBatch of B members against B lone learners")
     ap.add_argument("--ns", type=lambda v: [int(x) for x in v.split(",")], default=None, help="rows of the pool, with --batch (264,4096); trajectories, with --validate (16,256)")
+    ap.add_argument("--wide", action="store_true", help="with --batch: the [9, 256, 256, 6] network, a WideLearnerBatch against B lone wide learners")
     ap.add_argument("--validate", action="store_true", help="with --batch: time LearnerBatch.rollout against B lone handles' model_rollout")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=200)
@@ -220,6 +225,8 @@ def main():
     o = ap.parse_args()
     if o.validate and not o.batch:
         ap.error("--validate goes with --batch")
+    if o.wide and (not o.batch or o.validate):
+        ap.error("--wide goes with --batch, not with --validate (trajectory validation of wide members is not built)")
     o.ns = o.ns or ([16, 256] if o.validate else [264, 4096])
     if o.batch and not o.dry_run:
         return time_validate(o) if o.validate else time_batch(o)

@@ -101,7 +101,9 @@ def run(o):
     episodes, figures = [], []
     by_episode = getattr(o, "kfold_episode", False)
     # rates x folds learned controllers, one network each: they share the task and the Philox key, so only the networks tell them apart
-    folds_ctl = m.BatchHandle.learned(len(o.lrs) * o.kfold, model.mlp(), "nnauv", k=o.samples, seeds=[task["seed"]] * (len(o.lrs) * o.kfold),
+    # (the learned point mass: BatchHandle.learned(model="mlp"); its narrow networks only — grid_search refuses a wide model's episode=)
+    kind = dict(model="mlp", a_dim=task["a_dim"]) if o.model == "point_mass" else dict(model="nnauv")
+    folds_ctl = m.BatchHandle.learned(len(o.lrs) * o.kfold, model.mlp(), k=o.samples, seeds=[task["seed"]] * (len(o.lrs) * o.kfold), **kind,
                                       **{k: v for k, v in task.items() if k not in ("s_dim", "a_dim", "seed")}) if by_episode else None
     for r in range(o.rounds):
         X, U, Cs = cont.run_episode(x0, o.steps, plant=fossen)
@@ -162,11 +164,12 @@ def main(argv=None, on_round=None):
     ap.add_argument("--kfold", type=int, default=0, help="K >= 2: choose each round's learning rate among --lrs by K-fold cross-validation (LearnerBase.grid_search)")
     ap.add_argument("--lrs", type=lambda v: [float(x) for x in v.split(",")], default=None, help="a,b,c: the learning rates --kfold chooses from")
     ap.add_argument("--kfold-val", action="store_true", help="with --kfold: choose the rate by the folds' H-step open-loop error on the round's episode (LearnerBase.validate_fold)")
-    ap.add_argument("--kfold-episode", action="store_true", help="with --kfold (--model auv): choose the rate by a short closed-loop episode of every fold's network on the plant (LearnerBase.episode_fold)")
+    ap.add_argument("--kfold-episode", action="store_true", help="with --kfold (--model auv, or point_mass at --hidden 16 / 32): choose the rate by a short closed-loop episode of every fold's network on the plant (LearnerBase.episode_fold)")
     ap.add_argument("--episode-steps", type=int, default=10, help="steps of the --kfold-episode episodes")
     o = ap.parse_args(argv)
-    if o.kfold_episode and (not o.kfold or o.kfold_val or o.model != "auv" or o.episode_steps < 1):
-        ap.error("--kfold-episode goes with --kfold and --model auv, not with --kfold-val, and needs --episode-steps >= 1")
+    if o.kfold_episode and (not o.kfold or o.kfold_val or (o.model == "point_mass" and o.hidden == 256) or o.episode_steps < 1):
+        ap.error("--kfold-episode goes with --kfold (not with --model point_mass --hidden 256: the wide network's folds have no episode "
+                 "harness), not with --kfold-val, and needs --episode-steps >= 1")
     if o.kfold_val and (not o.kfold or o.steps < o.horizon):
         ap.error("--kfold-val goes with --kfold and needs --steps >= --horizon")
     if bool(o.kfold) != bool(o.lrs):

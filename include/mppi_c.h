@@ -36,7 +36,7 @@ extern "C" {
 #define MPPI_ABI_VERSION 5 /* 5: MPPI_TUNE_FUSED_STEP / _ARMED_US / _ARMED_ALWAYS / _PRELAUNCH (no entry point changed), mppi_run_episode / mppi_batch_run_episode
                               (added; no entry point changed), mppi_learner_gradients and the [in, 256, 256, out] learner (added; no entry point changed),
                               mppi_learner_batch_* (added; no entry point changed), mppi_create_batch_learned / mppi_batch_set_mlp (added; no entry point changed),
-                              mppi_learner_wide_batch_* (added; no entry point changed);
+                              mppi_learner_wide_batch_* (added; no entry point changed), mppi_create_batch_mlp (added; no entry point changed);
                               4: mppi_shard_step (one call per sharded step, the caller's collectives as function pointers), mppi_learner_save /
                               _load / _peek, MPPI_TUNE_TRACE (roctx ranges); mppi_set_mlp orders against the last step's stream;
                               3: the 13-state AUV family (MPPI_MODEL_AUV / _NN_AUV, mppi_auv_desc), StaticQuatCost / ElipseCost3D state costs,
@@ -485,6 +485,34 @@ mppi_status mppi_create_batch_learned(const mppi_config *cfgs, int n, mppi_handl
  * out of range, MPPI_ERR_INVALID_ARG and nothing changes); orders against the streams as mppi_set_mlp does; takes effect with the next
  * step. */
 mppi_status mppi_batch_set_mlp(mppi_handle *h, int member, const mppi_mlp_desc *mlp);
+
+/* ---- batched learned point-mass controllers: one MLP per member ---------------------------------------------------------------------
+ * B controllers of MPPI_MODEL_MLP (s_dim = 2 a_dim), member m with its OWN network and normalisation cfgs[m].mlp, stepped in the same two
+ * launches as one. An entry point of its own: mppi_create_batch, mppi_create_batch_configs and mppi_create_batch_learned keep refusing
+ * MPPI_MODEL_MLP word for word. Member m is bit for bit the lone handle mppi_create(&cfgs[m]) fed the same x, goal and sequence on the
+ * same step counter - sample costs, beta, eta, U' and u - where that handle runs
+ *   the [3a, 256, 256, 2a] network, a_dim 1..3:  k_rollout_mlp2<A, DIAG, SRC_PHILOX>, its DEFAULT matrix-core kernel (the batch runs the same
+ *                                                kernel body with a member axis, k_rollout_mlp2_batch<A, DIAG>);
+ *   Dense(16) x 1..3, a_dim 1..4:                k_rollout_mlp_small<A, 16>, its default (k_rollout_mlp_small_batch<A, 16>);
+ *   Dense(32) x 1..3, a_dim 1..4:                k_rollout_mlp_small<A, 32>, the handle tuned MPPI_TUNE_MLP32_VALU = 1; against that handle's
+ *                                                default k_rollout_mlp32_pc a member agrees to rounding, inside the bars both kernels are
+ *                                                tested to against fp64, not bit for bit.
+ * Members never interact.
+ *   per member: seed, goal, lambda, gamma, upsilon, sigma, the diagonal Q, and the network's weights and normalisation;
+ *   shared (else MPPI_ERR_INVALID_ARG naming the field, e.g. "cfgs[1].mlp.widths"): what mppi_create_batch_configs shares, and the
+ *     network's shape (mlp.n_layers, mlp.widths).
+ * The handle is an ordinary batched handle: mppi_batch_next / _next_device / _set_goals / _get/_set_action_sequences / _debug_get /
+ * _set_mlp / _run_episode / _run_episode_plant, mppi_get/set_step_counter, mppi_set_action_limits, mppi_synchronize,
+ * mppi_profile_begin/end, mppi_rollout_kernel_name ("mppi::k_rollout_mlp2_batch<3, true>") and mppi_destroy serve it.
+ * mppi_batch_run_episode steps member m's state with member m's own network; in mppi_batch_run_episode_plant a learned plant stays shared.
+ * MPPI_ERR_UNSUPPORTED, before anything is allocated, the message naming the cause: another model kind (POINT_MASS, AUV:
+ * mppi_create_batch_configs serves them; NN_AUV, NN_AUV_SPEED: mppi_create_batch_learned), the {256, 256} network at a_dim = 4 (the lone
+ * handle runs k_rollout_mlp there, which this batch does not carry), normalize_cost, MPPI_FLAG_MLP_BF16X3, MPPI_FLAG_FP_CONTRACT,
+ * shard_count > 1, a dense Q (q_is_full), a state cost other than the quadratic one, more than 1024 tiles per member; on the handle what
+ * any batch refuses (the tunings of the lone step, MPPI_TUNE_MLP32_VALU, MPPI_TUNE_MLP_V1, the sequence filter, the transition log,
+ * mppi_set_mlp). MPPI_ERR_INVALID_ARG: NULL cfgs / out, n < 1, a member without cfg.mlp, a member whose shared field or network shape
+ * differs from member 0's, sigma diagonal for some members and dense for others, n * k too large. */
+mppi_status mppi_create_batch_mlp(const mppi_config *cfgs, int n, mppi_handle **out);
 
 /* ---- closed-loop episodes: n_steps control steps on the device, the handle's own model as the plant ---------------------------------
  * For t = 0 .. n_steps-1, per member:

@@ -142,6 +142,8 @@ SIGNATURES = {
     # ... of the learned 13-state models, one network per member (BatchHandle.learned, BatchHandle.set_mlp)
     "mppi_create_batch_learned": (C.c_int, [C.POINTER(Config), C.c_int, C.POINTER(_H)]),
     "mppi_batch_set_mlp": (C.c_int, [_H, C.c_int, C.POINTER(MlpDesc)]),
+    # ... of the learned point mass, one network per member (BatchHandle.learned(model="mlp"))
+    "mppi_create_batch_mlp": (C.c_int, [C.POINTER(Config), C.c_int, C.POINTER(_H)]),
     # closed-loop episodes on the device (Handle.run_episode, BatchHandle.run_episode)
     "mppi_run_episode": (C.c_int, [_H, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
     "mppi_batch_run_episode": (C.c_int, [_H, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
@@ -804,24 +806,50 @@ class BatchHandle(_HandleBase):
     _LEARNED = {"nnauv": (MODEL_NN_AUV, 16, 13), "nnauv_speed": (MODEL_NN_AUV_SPEED, 15, 6)}  # kind, network inputs, outputs
 
     @classmethod
-    def learned(cls, n, nets, model="nnauv", *, k, tau, goals=None, tuning=None, normalize_cost=False, shard_count=1, mlp_bf16x3=False,
-                fp_contract=False, **cfg):
+    def learned(cls, n, nets, model="nnauv", *, k, tau, a_dim=None, goals=None, tuning=None, normalize_cost=False, shard_count=1,
+                mlp_bf16x3=False, fp_contract=False, **cfg):
         """mppi_create_batch_learned: n controllers of a learned 13-state model ("nnauv": NNAUVModel, "nnauv_speed": NNAUVModelSpeed), member m
         with its OWN network. nets: one dict in the `nnauv=` format of Handle (every member gets it) or n of them, all of one shape;
         k, tau and the other keywords as batch_configs' (seeds, goal, lam(s), gamma(s), upsilon(s), sigma(s), Q(s), quat_cost, ellipse3d, ...).
-        Member m is bit for bit the lone Handle of its config and network on k_rollout_gen (include/mppi_c.h)."""
-        if model not in cls._LEARNED:
-            raise ValueError('model must be "nnauv" or "nnauv_speed", not %r' % (model,))
-        kind, n_in, n_out = cls._LEARNED[model]
+        Member m is bit for bit the lone Handle of its config and network on k_rollout_gen (include/mppi_c.h).
+        model="mlp" with a_dim (mppi_create_batch_mlp): n controllers of the learned point mass (s_dim = 2 a_dim), nets in the `mlp=` format
+        of Handle: [3a, 256, 256, 2a] (a_dim <= 3) or 1-3 hidden layers of 16 or 32. Member m is bit for bit Handle(..., mlp=nets[m]) on its
+        default kernel (Dense(32): the Handle tuned mlp32_valu = 1). A network of the wrong shape raises ValueError before the library is
+        called."""
+        if model == "mlp":
+            if a_dim is None or int(a_dim) < 1:
+                raise ValueError('model="mlp" needs a_dim >= 1 (s_dim = 2 a_dim)')
+            a, kind = int(a_dim), MODEL_MLP
+            s, n_in, n_out = 2 * a, 3 * a, 2 * a
+        elif model in cls._LEARNED:
+            if a_dim is not None and int(a_dim) != 6:
+                raise ValueError("the learned 13-state models have a_dim = 6")
+            (kind, n_in, n_out), s, a = cls._LEARNED[model], 13, 6
+        else:
+            raise ValueError('model must be "nnauv", "nnauv_speed" or "mlp", not %r' % (model,))
         nets = [nets] * n if isinstance(nets, dict) else list(nets)
         if len(nets) != n:
             raise MppiError(ERR_INVALID_ARG, "nets must hold n = %d networks (or be one dict), not %d" % (n, len(nets)))
+        if model == "mlp":  # the shapes, before any device work
+            shapes = [None if net is None else [tuple(np.shape(w)) for w in net["W"]] for net in nets]
+            for m, sh in enumerate(shapes):
+                if sh is None:
+                    continue
+                chain = all(len(x) == 2 for x in sh) and all(sh[l][1] == sh[l + 1][0] for l in range(len(sh) - 1))
+                if not sh or not chain or sh[0][0] != n_in or sh[-1][1] != n_out:
+                    raise ValueError("nets[%d]: the kernels must chain from %d inputs (s_dim + a_dim) to %d outputs (s_dim), not %s"
+                                     % (m, n_in, n_out, sh))
+                if [np.size(b) for b in nets[m]["b"]] != [x[1] for x in sh]:
+                    raise ValueError("nets[%d]: one bias vector per layer, of the layer's width" % m)
+                first = next(x for x in shapes if x is not None)
+                if sh != first:
+                    raise ValueError("nets[%d]: every member's network has the shape of the first (%s), not %s" % (m, first, sh))
         self = cls.__new__(cls)
         lib = self.lib = load()
         self.h = _H()
-        self.n, self.k, self.tau, self.s, self.a = n, k, tau, 13, 6
+        self.n, self.k, self.tau, self.s, self.a = n, k, tau, s, a
         self._mlp_io = (n_in, n_out)
-        cfgs, keep = batch_configs(n, k, tau, 13, 6, **cfg)
+        cfgs, keep = batch_configs(n, k, tau, s, a, **cfg)
         for m in range(n):
             cfgs[m].model_kind = kind
             cfgs[m].normalize_cost, cfgs[m].shard_count = int(bool(normalize_cost)), shard_count
@@ -830,7 +858,7 @@ class BatchHandle(_HandleBase):
                 desc, held = _mlp_desc(nets[m], n_in, n_out)
                 keep += held
                 cfgs[m].mlp = C.pointer(desc)
-        st = lib.mppi_create_batch_learned(cfgs, int(n), C.byref(self.h))
+        st = (lib.mppi_create_batch_mlp if model == "mlp" else lib.mppi_create_batch_learned)(cfgs, int(n), C.byref(self.h))
         if st != OK:
             self.h = _H()
             self._check(st, None)
@@ -850,8 +878,9 @@ class BatchHandle(_HandleBase):
         del held
 
     def load_learners(self, batch, model):
-        """Every member's weights of the LearnerBatch `batch` (as many members as this handle), with the normalisation of `model`
-        (LearnerBatch.model_desc: a model object or a dict with xmean, xstd, ymean, ystd), into the controllers, through the host."""
+        """Every member's weights of the LearnerBatch or WideLearnerBatch `batch` (as many members as this handle; what is read of it is
+        .B and .get_weights(m)), with the normalisation of `model` (LearnerBatch.model_desc: a model object or a dict with xmean, xstd,
+        ymean, ystd), into the controllers, through the host."""
         if batch.B != self.n:
             raise MppiError(ERR_INVALID_ARG, "load_learners: the learner batch has %d members, the controllers %d" % (batch.B, self.n))
         d = LearnerBatch.model_desc(model)

@@ -26,6 +26,7 @@ MLP_ONLY_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # the 13-state units, compiled with the MLP units' flags (the batched AUV step is the same kernel text as the gen unit's)
 MLP_STEMS = ("gen", "batch_gen", "batch_nn")
 UNITS = ([("mppi_launch_mlp.hip", ["MPPI_UNIT_A=%d" % a], "mlp_a%d" % a) for a in (3, 2, 1, 4)]
+         + [("mppi_launch_batch_mlp.hip", ["MPPI_UNIT_A=%d" % a], "batch_mlp_a%d" % a) for a in (3, 2, 1, 4)]
          + [("mppi_launch_pc.hip", ["MPPI_UNIT_A=%d" % a], "pc_a%d" % a) for a in (4, 3, 2, 1)]
          + [("mppi_launch_batch.hip", ["MPPI_UNIT_A=%d" % a], "batch_a%d" % a) for a in (4, 3, 2, 1)]
          + [("mppi_launch_step.hip", ["MPPI_UNIT_A=%d" % a], "step_a%d" % a) for a in (4, 3, 2, 1)]
@@ -41,7 +42,8 @@ UNITS = ([("mppi_launch_mlp.hip", ["MPPI_UNIT_A=%d" % a], "mlp_a%d" % a) for a i
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mppi_device.hip.h", "mppi_ablate.hip.h", "mppi_kernels.hip.h", "mppi_mlp2.hip.h", "mppi_mlp_small.hip.h", "mppi_mlp32.hip.h",
            "mppi_handle.hip.h", "mppi_capi.hip.h", "mppi_step.hip.h", "mppi_gen.hip.h", "mppi_mfma32.hip.h", "mppi_bx3.hip.h", "mppi_mlp32b.hip.h", "mppi_rollout_pc.inc",
-           "mppi_rollout_auv_pc.inc", "mppi_episode_plant.hip.h", "mppi_model_rollout.hip.h", "mppi_learner.hip.h", "mppi_nn_batch.hip.h"]
+           "mppi_rollout_auv_pc.inc", "mppi_episode_plant.hip.h", "mppi_model_rollout.hip.h", "mppi_learner.hip.h", "mppi_nn_batch.hip.h",
+           "mppi_mlp2_body.inc", "mppi_mlp_batch.hip.h"]
 ARCH = "gfx950"
 
 
@@ -90,7 +92,7 @@ def _compile_all(objdir, extra, force, verbose):
         obj = os.path.join(objdir, stem + ".o")
         if not force and os.path.exists(obj) and all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in _deps(src)):
             return obj
-        cmd = [cc, *flags(extra), *(MLP_FLAGS if stem.startswith("mlp_") or stem in MLP_STEMS else []), *(MLP_ONLY_FLAGS if stem.startswith("mlp_") or stem in MLP_STEMS else []), *["-D" + d for d in defs], "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [cc, *flags(extra), *(MLP_FLAGS + MLP_ONLY_FLAGS if stem.startswith(("mlp_", "batch_mlp_")) or stem in MLP_STEMS else []), *["-D" + d for d in defs], "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -149,7 +149,7 @@ extern "C" void mppi_destroy(mppi_handle *h)
 }
 
 // Upload a learned model's weights and normalisation (mppi_create: allocate = true; mppi_set_mlp: the same buffers again).
-// member >= 0 (a learned batch, mppi_create_batch_learned): member m's network in the same layout at d_mlp_w + m * nn_stride, its MlpDev at
+// member >= 0 (a learned batch, mppi_create_batch_learned / mppi_create_batch_mlp): member m's network in the same layout at d_mlp_w + m * nn_stride, its MlpDev at
 // dM + m and its padded layer pointers at d_nn_args + m (allocate: all B at once, with member 0); hm / small_args mirror member 0.
 static mppi_status upload_mlp(mppi_handle *h, const mppi_mlp_desc *d, bool allocate, int member = -1)
 {
@@ -184,6 +184,10 @@ static mppi_status upload_mlp(mppi_handle *h, const mppi_mlp_desc *d, bool alloc
             hm.ld[l] = ld;
             hm.Wl[l] = sa.W[l] = p + at;
             hm.bl[l] = sa.b[l] = p + at + nw;
+        }
+        if (!h->mlp_small && !nnauv) { // the {256, 256, s} network of k_rollout_mlp2_batch (mppi_create_batch_mlp)
+            hm.W1 = hm.Wl[0]; hm.b1 = hm.bl[0]; hm.W2 = hm.Wl[1]; hm.b2 = hm.bl[1];
+            hm.W3 = hm.Wl[2]; hm.b3 = hm.bl[2];
         }
         for (int i = 0; i < kMaxS + kMaxA; ++i) { hm.xmean[i] = 0.f; hm.xstd[i] = 1.f; }
         for (int i = 0; i < nin; ++i) { hm.xmean[i] = d->xmean ? d->xmean[i] : 0.f; hm.xstd[i] = d->xstd ? d->xstd[i] : 1.f; }
@@ -426,7 +430,8 @@ static mppi_status derive_handle(const mppi_config *cfg, mppi_handle **out)
 // Member m's constants from its config, the one validation of a member: its temperature, its Sigma, and that it runs the kernel instance
 // member 0 picked (sigma_diag, the effective Q form; member 0 is filled into h->hc and sets both). A failure is
 // g_create_err, naming the member if `named`.
-static mppi_status member_consts(const mppi_config *cfg, int m, bool named, mppi_handle *h, DevConsts &c)
+// mixed: the status of a member whose effective Sigma or Q form differs from member 0's (mppi_create_batch_mlp: MPPI_ERR_INVALID_ARG).
+static mppi_status member_consts(const mppi_config *cfg, int m, bool named, mppi_handle *h, DevConsts &c, mppi_status mixed = MPPI_ERR_UNSUPPORTED)
 {
     const std::string who = named ? "batched controllers: member " + std::to_string(m) + ": " : "";
     if (!temperature_ok(cfg)) return fail(nullptr, MPPI_ERR_INVALID_ARG, who + kBadTemperature);
@@ -434,11 +439,11 @@ static mppi_status member_consts(const mppi_config *cfg, int m, bool named, mppi
     if (!fill_consts(cfg, h, c, diag)) return fail(nullptr, MPPI_ERR_SINGULAR_SIGMA, who + "sigma is singular");
     if (m == 0) { h->sigma_diag = diag; return MPPI_OK; } // (c is h->hc: member 0 sets what the others are compared with)
     if (diag != h->sigma_diag)
-        return fail(nullptr, MPPI_ERR_UNSUPPORTED,
+        return fail(nullptr, mixed,
             "batched controllers: sigma must be diagonal for every member or dense for every member (member " + std::to_string(m) +
             " differs from member 0)");
     if (c.q_full != h->hc.q_full)
-        return fail(nullptr, MPPI_ERR_UNSUPPORTED,
+        return fail(nullptr, mixed,
                                                        "batched controllers: Q must be diagonal for every member or dense for every "
                                                        "member (member " + std::to_string(m) +
                                                       " differs from member 0; a dense Q without off-diagonal entries counts as diagonal)");
@@ -681,17 +686,40 @@ static const char *learned_batch_refusal(const mppi_config *cfg)
     return nullptr;
 }
 
-// learned: mppi_create_batch_learned's batch — the learned 13-state models, member m with its own network cfgs[m].mlp
-static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_members, mppi_handle **out, bool learned = false)
+// why cfg cannot be a member of a batch of learned point masses (mppi_create_batch_mlp; NULL: it can, as far as the config alone tells)
+static const char *mlp_batch_refusal(const mppi_config *cfg)
+{
+    switch (cfg->model_kind) {
+    case MPPI_MODEL_MLP: break;
+    case MPPI_MODEL_POINT_MASS: return "batched MLP controllers: model POINT_MASS has no network: mppi_create_batch_configs serves it";
+    case MPPI_MODEL_AUV: return "batched MLP controllers: model AUV has no network: mppi_create_batch_configs serves it";
+    case MPPI_MODEL_NN_AUV: return "batched MLP controllers: model NNAUV is a 13-state model: mppi_create_batch_learned serves it";
+    case MPPI_MODEL_NN_AUV_SPEED: return "batched MLP controllers: model NNAUVSpeed is a 13-state model: mppi_create_batch_learned serves it";
+    default: return nullptr; // (mppi_create reports it)
+    }
+    if (cfg->normalize_cost) return "batched MLP controllers: normalize_cost is not supported";
+    if (cfg->flags & MPPI_FLAG_MLP_BF16X3) return "batched MLP controllers: MPPI_FLAG_MLP_BF16X3 is not supported";
+    if (cfg->flags & MPPI_FLAG_FP_CONTRACT) return "batched MLP controllers: MPPI_FLAG_FP_CONTRACT is not supported";
+    if (cfg->shard_count > 1) return "batched MLP controllers: sharding (shard_count > 1) is not supported";
+    if (cfg->state_cost_kind != MPPI_STATE_COST_QUADRATIC) return "batched MLP controllers: the quadratic state cost only (state_cost_kind)";
+    if (cfg->q_is_full) return "batched MLP controllers: a dense Q (q_is_full) is not supported (the MLP rollouts take a diagonal Q)";
+    return nullptr;
+}
+
+// learned = 1: mppi_create_batch_learned's batch — the learned 13-state models, member m with its own network cfgs[m].mlp;
+// learned = 2: mppi_create_batch_mlp's — the learned point mass, likewise
+static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_members, mppi_handle **out, int learned = 0)
 {
     for (int m = 0; m < n; ++m)
         if (cfgs[m].struct_size != sizeof(mppi_config)) return fail(nullptr, MPPI_ERR_INVALID_ARG,
             "mppi_config.struct_size mismatch (use mppi_config_init)");
     if (learned) {
-        if (const char *why = learned_batch_refusal(&cfgs[0])) return fail(nullptr, MPPI_ERR_UNSUPPORTED, why);
+        if (const char *why = learned == 2 ? mlp_batch_refusal(&cfgs[0]) : learned_batch_refusal(&cfgs[0]))
+            return fail(nullptr, MPPI_ERR_UNSUPPORTED, why);
         for (int m = 0; m < n; ++m) {
             const mppi_mlp_desc *d = cfgs[m].mlp;
-            const std::string who = "batched learned controllers: member " + std::to_string(m) + ": ";
+            const std::string who = std::string(learned == 2 ? "batched MLP controllers: member " : "batched learned controllers: member ") +
+                std::to_string(m) + ": ";
             if (!d) return fail(nullptr, MPPI_ERR_INVALID_ARG, who + "cfg.mlp is NULL (every member brings its own network)");
             if (!d->widths || !d->W || !d->b) return fail(nullptr, MPPI_ERR_INVALID_ARG, who + "cfg.mlp needs widths, W, b");
             for (int l = 0; l < d->n_layers && l < kMlpSmallMaxLayers; ++l)
@@ -699,7 +727,7 @@ static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_member
         }
     }
     for (int m = 1; m < n; ++m)
-        if (const char *f = batch_shared_diff(&cfgs[0], &cfgs[m], learned))
+        if (const char *f = batch_shared_diff(&cfgs[0], &cfgs[m], learned != 0))
             return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: cfgs[" + std::to_string(m) + "]." + f +
                 " differs from cfgs[0]." + f + " (every member shares it)");
     const mppi_config *cfg = &cfgs[0];
@@ -712,6 +740,11 @@ static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_member
         "above 512 tiles)");
     if (!learned && h->is_gen && !auv_batch_eligible(h)) return refuse(MPPI_ERR_UNSUPPORTED,
         "batched controllers: the Fossen AUV model is batched on its two-wave rollout (k_rollout_auv_pc) only");
+    if (learned == 2 && !h->mlp_small && !h->mlp_v2) return refuse(MPPI_ERR_UNSUPPORTED,
+        "batched MLP controllers: the {256, 256} network at a_dim = 4 is not supported (the lone handle runs k_rollout_mlp there, which this "
+        "batch does not carry; a_dim <= 3)");
+    if (learned == 2 && !h->no_rollout.empty()) return refuse(MPPI_ERR_UNSUPPORTED, "batched MLP controllers: " + h->no_rollout);
+    if (learned == 2 && n > 65535) return refuse(MPPI_ERR_INVALID_ARG, "batched MLP controllers: at most 65535 members");
     if (h->nbp > 1024) return refuse(MPPI_ERR_UNSUPPORTED,
         "batched controllers: at most 1024 tiles (k = 65536) per member (the finish combines a member's records in one pass)");
     if ((long long)h->nb * n > (1ll << 30) / 64) return refuse(MPPI_ERR_INVALID_ARG, "batched controllers: n * k too large");
@@ -719,9 +752,10 @@ static mppi_status create_batch(const mppi_config *cfgs, int n, bool name_member
     std::vector<DevConsts> consts(n);
     consts[0] = h->hc;
     for (int m = 1; m < n; ++m)
-        if (mppi_status st = member_consts(&cfgs[m], m, true, h, consts[m]); st != MPPI_OK) { mppi_destroy(h); return st; }
+        if (mppi_status st = member_consts(&cfgs[m], m, true, h, consts[m], learned == 2 ? MPPI_ERR_INVALID_ARG : MPPI_ERR_UNSUPPORTED);
+            st != MPPI_OK) { mppi_destroy(h); return st; }
     h->batch = n;
-    h->nn_batch = learned ? 1 : 0;
+    h->nn_batch = learned;
     h->fuse_step = 0; // the two launches, always
     mppi_status st = allocate_handle(h, cfg, n, consts.data());
     for (int m = 1; learned && st == MPPI_OK && m < n; ++m) st = upload_mlp(h, cfgs[m].mlp, false, m);
@@ -736,13 +770,22 @@ extern "C" mppi_status mppi_create_batch_learned(const mppi_config *cfgs, int n,
     if (!cfgs || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfgs/out is NULL");
     *out = nullptr;
     if (n < 1) return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: n must be >= 1");
-    return create_batch(cfgs, n, true, out, true);
+    return create_batch(cfgs, n, true, out, 1);
+}
+
+// ---- batched learned point-mass controllers (include/mppi_c.h; the kernels: mppi_mlp_batch.hip.h) -------------------------------------
+extern "C" mppi_status mppi_create_batch_mlp(const mppi_config *cfgs, int n, mppi_handle **out)
+{
+    if (!cfgs || !out) return fail(nullptr, MPPI_ERR_INVALID_ARG, "cfgs/out is NULL");
+    *out = nullptr;
+    if (n < 1) return fail(nullptr, MPPI_ERR_INVALID_ARG, "batched controllers: n must be >= 1");
+    return create_batch(cfgs, n, true, out, 2);
 }
 
 extern "C" mppi_status mppi_batch_set_mlp(mppi_handle *h, int member, const mppi_mlp_desc *d)
 {
     MPPI_BATCH_ONLY(h);
-    if (!h->nn_batch) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp: not a batch of learned controllers (mppi_create_batch_learned)");
+    if (!h->nn_batch) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp: not a batch of learned controllers (mppi_create_batch_learned / mppi_create_batch_mlp)");
     if (member < -1 || member >= h->batch) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp: member out of range");
     if (!d || !d->widths || !d->W || !d->b) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp needs widths, W, b");
     if (d->n_layers != h->hm.n_layers) return fail(h, MPPI_ERR_INVALID_ARG, "mppi_batch_set_mlp: the layer count is fixed at creation");

@@ -172,12 +172,18 @@ inline bool auv_batch_eligible(const mppi_handle *h)
 // a batch of learned 13-state controllers (mppi_create_batch_learned): what k_rollout_nn_batch runs
 inline bool nn_batch_eligible(const mppi_handle *h)
 {
-    return h->is_gen && h->nn_batch && h->d_nn_args != nullptr && !h->normalize && h->shard_count == 1 && !h->mlp_bx3;
+    return h->is_gen && h->nn_batch == 1 && h->d_nn_args != nullptr && !h->normalize && h->shard_count == 1 && !h->mlp_bx3;
+}
+// a batch of learned point masses (mppi_create_batch_mlp): what k_rollout_mlp2_batch / k_rollout_mlp_small_batch run
+inline bool mlp_batch_eligible(const mppi_handle *h)
+{
+    return !h->is_gen && h->nn_batch == 2 && h->hc.model_kind == MPPI_MODEL_MLP && h->no_rollout.empty() && (h->mlp_small ? h->d_nn_args != nullptr
+        : h->mlp_v2 != 0) && !h->normalize && h->shard_count == 1 && !h->mlp_bx3;
 }
 // the batched step serves the handle (why not: batch_step's message)
 inline bool batch_eligible(const mppi_handle *h)
 {
-    return h->nn_batch ? nn_batch_eligible(h) : h->is_gen ? auv_batch_eligible(h) : pc_eligible(h);
+    return h->nn_batch == 2 ? mlp_batch_eligible(h) : h->nn_batch ? nn_batch_eligible(h) : h->is_gen ? auv_batch_eligible(h) : pc_eligible(h);
 }
 
 // ---- host functions of mppi_capi_step.hip that other units call (comments at the definitions)
@@ -195,8 +201,10 @@ mppi_status enqueue_partials(mppi_handle *h, hipStream_t st, int src, const floa
 mppi_status ensure_eps(mppi_handle *h);
 mppi_status finish_step(mppi_handle *h, hipStream_t st, const Finish &f);
 mppi_status plain_step(mppi_handle *h, hipStream_t st, int src, const float *x_dev, const float *eps, float *u_dev, bool xchg = false);
-// ---- ... and of mppi_capi_debug.hip: one launch of k_mlp_step_ref, 64 samples per workgroup (the learned point-mass model as a plant)
-void mlp_step_ref(mppi_handle *h, hipStream_t st, const float *x, int kx, const float *v, int k, float *scratch, float *out_next);
+// ---- ... and of mppi_capi_debug.hip: one launch of k_mlp_step_ref, 64 samples per workgroup (the learned point-mass model as a plant).
+// member_stride 0: one network (h->dM) for every row; 1: row i through the network of member i (a learned batch as its own plant)
+void mlp_step_ref(mppi_handle *h, hipStream_t st, const float *x, int kx, const float *v, int k, float *scratch, float *out_next,
+                  int member_stride = 0);
 
 } // namespace mppi_capi
 using namespace mppi_capi;

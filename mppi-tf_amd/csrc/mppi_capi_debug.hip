@@ -93,9 +93,10 @@ struct DevBuf {
 };
 
 namespace mppi_capi {
-void mlp_step_ref(mppi_handle *h, hipStream_t st, const float *x, int kx, const float *v, int k, float *scratch, float *out_next)
+void mlp_step_ref(mppi_handle *h, hipStream_t st, const float *x, int kx, const float *v, int k, float *scratch, float *out_next,
+                  int member_stride)
 {
-    hipLaunchKernelGGL(k_mlp_step_ref, dim3((k + 63) / 64), dim3(64), 0, st, h->dC, h->dM, x, kx, v, k, scratch, out_next);
+    hipLaunchKernelGGL(k_mlp_step_ref, dim3((k + 63) / 64), dim3(64), 0, st, h->dC, h->dM, x, kx, v, k, scratch, out_next, member_stride);
 }
 } // namespace mppi_capi
 

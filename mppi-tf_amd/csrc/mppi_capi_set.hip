@@ -59,7 +59,7 @@ extern "C" mppi_status mppi_rollout_kernel_name(const mppi_handle *h, char *buf,
     const mppi_unit_a *u = unit(h);
     const char *name = nullptr;
     switch (rollout_route(h, SRC_PHILOX, nullptr, true)) {
-    case ROUTE_BATCH: name = h->nn_batch ? mppi_batch_nn_name(h) : h->is_gen ? mppi_batch_auv_name(h) : u ? u->batch_name(h) : nullptr; break;
+    case ROUTE_BATCH: name = h->nn_batch == 2 ? (u ? u->batch_mlp_name(h) : nullptr) : h->nn_batch ? mppi_batch_nn_name(h) : h->is_gen ? mppi_batch_auv_name(h) : u ? u->batch_name(h) : nullptr; break;
     case ROUTE_STEP: name = u ? u->step_name(h, STEP_FUSE) : nullptr; break;
     case ROUTE_PC: name = u ? u->pc_name(h, h->normalize ? PC_PASS_WEIGHTS : PC_PASS_PLAIN) : nullptr; break;
     case ROUTE_TILE: name = u ? u->tile_name(h, SRC_PHILOX, h->normalize ? MODE_COST_ONLY : MODE_ROLLOUT) : nullptr; break;
@@ -243,7 +243,8 @@ extern "C" mppi_status mppi_set_tuning(mppi_handle *h, int what, int value)
                         : (what == MPPI_TUNE_PRELAUNCH && value != 0) ? "prelaunch"
                         : (what == MPPI_TUNE_FORCE_TILE_KERNEL && value != 0) ? "force_tile_kernel"
                         : (h->is_gen && what == MPPI_TUNE_GEN_ONE_WAVE && value != 0) ? "gen_one_wave"
-                        : (h->is_gen && what == MPPI_TUNE_MLP32_VALU && value != 0) ? "mlp32_valu" : nullptr;
+                        : ((h->is_gen || h->nn_batch == 2) && what == MPPI_TUNE_MLP32_VALU && value != 0) ? "mlp32_valu"
+                        : (h->nn_batch == 2 && what == MPPI_TUNE_MLP_V1 && value != 0) ? "mlp_v1" : nullptr;
         if (why) return fail(h, MPPI_ERR_UNSUPPORTED, std::string("tuning ") + why +
             ": a batched handle always runs the two-launch batched step");
     }

@@ -68,7 +68,7 @@ hipError_t quiesce(mppi_handle *h)
 // kernel family and action dimension, compiled in parallel); mppi_handle.hip.h declares their entry points, one row per action dimension.
 #define MPPI_UNIT_ROW(N)                                                                                                  \
     {mppi_tile_a##N, mppi_pc_a##N, mppi_mlp_a##N, mppi_step_a##N, mppi_batch_a##N, mppi_batch_finish_a##N, mppi_tile_name_a##N, \
-     mppi_pc_name_a##N, mppi_mlp_name_a##N, mppi_step_name_a##N, mppi_batch_name_a##N}
+     mppi_pc_name_a##N, mppi_mlp_name_a##N, mppi_step_name_a##N, mppi_batch_name_a##N, mppi_batch_mlp_a##N, mppi_batch_mlp_name_a##N}
 static const mppi_unit_a kUnits[4] = {MPPI_UNIT_ROW(1), MPPI_UNIT_ROW(2), MPPI_UNIT_ROW(3), MPPI_UNIT_ROW(4)};
 #undef MPPI_UNIT_ROW
 const mppi_unit_a *unit(const mppi_handle *h) { return h->a >= 1 && h->a <= 4 ? &kUnits[h->a - 1] : nullptr; }
@@ -545,7 +545,8 @@ extern "C" mppi_status mppi_next_with_noise(mppi_handle *h, const float *x, int 
 // why the batched step does not serve the handle as it stands (batch_eligible)
 static const char *kBatchStepRefusal(const mppi_handle *h)
 {
-    return h->nn_batch ? "batched step: the learned 13-state models run on k_rollout_nn_batch only"
+    return h->nn_batch == 2 ? "batched step: the learned point mass runs on k_rollout_mlp2_batch / k_rollout_mlp_small_batch only"
+         : h->nn_batch ? "batched step: the learned 13-state models run on k_rollout_nn_batch only"
          : h->is_gen   ? "batched step: the Fossen AUV model runs on k_rollout_auv_pc only"
                        : "batched step: the horizon exceeds what this producer count serves (tau <= 132 with 3 producers)";
 }
@@ -556,7 +557,8 @@ static mppi_status batch_step(mppi_handle *h, hipStream_t st, const float *x_dev
     if (!batch_eligible(h)) return fail(h, MPPI_ERR_UNSUPPORTED, kBatchStepRefusal(h));
     TraceRange step_range(h, "mppi:batch_step");
     const ProfSlot p = prof_slot(h); // the dispatches' own begin / end
-    HIP_TRY(h, h->nn_batch ? mppi_launch_batch_nn(h, st, p.rollout, x_dev)
+    HIP_TRY(h, h->nn_batch == 2 ? per_a(h, &mppi_unit_a::batch_mlp, st, p.rollout, x_dev)
+             : h->nn_batch ? mppi_launch_batch_nn(h, st, p.rollout, x_dev)
              : h->is_gen ? mppi_launch_batch_auv(h, st, p.rollout, x_dev) : per_a(h, &mppi_unit_a::batch, st, p.rollout, x_dev));
     HIP_TRY(h, h->is_gen ? mppi_launch_batch_finish_auv(h, st, h->U_cur(), h->U_other(), u_dev, p.finish)
                          : per_a(h, &mppi_unit_a::batch_finish, st, (const float *)h->U_cur(), h->U_other(), u_dev, p.finish));
@@ -725,7 +727,7 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
         }
         TraceRange plant_range(h, "mppi:plant");
         if (learned && mk == MPPI_MODEL_MLP) {
-            mlp_step_ref(stepper, st, x_t, B, u_t, B, scratch, x_next);
+            mlp_step_ref(stepper, st, x_t, B, u_t, B, scratch, x_next, (stepper == h && h->nn_batch) ? 1 : 0);
             HIP_TRY(h, hipGetLastError());
         } else if (learned && stepper == h && h->nn_batch) HIP_TRY(h, mppi_gen_model_step_members(h, st, x_t, u_t, B, scratch, x_next));
         else if (learned) HIP_TRY(h, mppi_gen_model_step(stepper, st, x_t, B, u_t, B, scratch, x_next));

@@ -3,7 +3,7 @@
 // (creation), mppi_capi_set.hip (setters, accessors), mppi_capi_step.hip (the control step), mppi_capi_shard.hip, mppi_capi_log.hip,
 // mppi_capi_debug.hip — behind one internal header, mppi_capi.hip.h;
 // mppi_launch_tile.hip / _pc.hip / _mlp.hip / _batch.hip instantiate one kernel family each for ONE action dimension per object
-// (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step, mppi_launch_batch_nn.hip the batched step of the learned 13-state models, mppi_episode.hip the plant of a closed-loop
+// (-DMPPI_UNIT_A=1..4), mppi_launch_gen.hip the generic-model kernels, mppi_launch_batch_gen.hip the batched AUV step, mppi_launch_batch_nn.hip the batched step of the learned 13-state models, mppi_launch_batch_mlp.hip that of the learned point mass (per action dimension), mppi_episode.hip the plant of a closed-loop
 // episode, mppi_episode_plant.hip the same with another handle's model as the plant, mppi_model_rollout.hip the open-loop rollout of the
 // handle's model (kernels and entry points). This header is what they share.
 #pragma once
@@ -133,7 +133,8 @@ struct mppi_handle {
     // the two batched launches (mppi_launch_batch.hip; the Fossen AUV model: mppi_launch_batch_gen.hip).
     int batch = 0;
     float *d_bx = nullptr, *d_bu = nullptr;
-    // a batch of learned 13-state controllers (mppi_create_batch_learned; mppi_launch_batch_nn.hip): member m's network is the lone upload
+    // a batch of learned controllers, one network per member — 1: the 13-state models (mppi_create_batch_learned; mppi_launch_batch_nn.hip),
+    // 2: the learned point mass (mppi_create_batch_mlp; mppi_launch_batch_mlp.hip): member m's network is the lone upload
     // layout at d_mlp_w + m * nn_stride, its MlpDev at dM + m, its padded layer pointers at d_nn_args + m (hm / small_args: member 0's)
     int nn_batch = 0;
     size_t nn_stride = 0; // floats
@@ -234,13 +235,15 @@ struct mppi_step_launch {
 #define MPPI_BATCH_FINISH_PARAMS mppi_handle *h, hipStream_t st, const float *U_in, float *U_out, float *u_dev, mppi_kev kev
 // The entry points of the per-a launch units (mppi_launch_{tile,pc,mlp,step,batch}.hip): X(NAME, result, parameters) is defined as
 // mppi_NAME_a1 .. mppi_NAME_a4, one per action dimension, each in its own object file; the *_name entries name what the launch would run.
-// The batched step (mppi_launch_batch.hip): every member's rollout in one launch, every member's finish in another.
+// The batched step (mppi_launch_batch.hip): every member's rollout in one launch, every member's finish in another; batch_mlp: the
+// rollouts of a batch of learned point masses, one network per member (mppi_launch_batch_mlp.hip), finished by batch_finish.
 #define MPPI_UNIT_ENTRIES(X)                                                                                                         \
     X(tile, hipError_t, MPPI_TILE_PARAMS) X(pc, hipError_t, MPPI_PC_PARAMS) X(mlp, hipError_t, MPPI_MLP_PARAMS)                       \
     X(step, hipError_t, MPPI_STEP_PARAMS) X(batch, hipError_t, MPPI_BATCH_PARAMS) X(batch_finish, hipError_t, MPPI_BATCH_FINISH_PARAMS) \
     X(tile_name, const char *, const mppi_handle *h, int src, int mode) X(pc_name, const char *, const mppi_handle *h, int pass)      \
     X(mlp_name, const char *, const mppi_handle *h, int src) X(step_name, const char *, const mppi_handle *h, int mode)               \
-    X(batch_name, const char *, const mppi_handle *h)
+    X(batch_name, const char *, const mppi_handle *h) X(batch_mlp, hipError_t, MPPI_BATCH_PARAMS)                                     \
+    X(batch_mlp_name, const char *, const mppi_handle *h)
 #define MPPI_DECL_A(NAME, R, ...) R mppi_##NAME##_a1(__VA_ARGS__); R mppi_##NAME##_a2(__VA_ARGS__); R mppi_##NAME##_a3(__VA_ARGS__); R mppi_##NAME##_a4(__VA_ARGS__);
 #define MPPI_MEMBER(NAME, R, ...) R (*NAME)(__VA_ARGS__);
 MPPI_UNIT_ENTRIES(MPPI_DECL_A)

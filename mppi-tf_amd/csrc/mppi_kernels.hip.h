@@ -648,10 +648,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #if defined(MPPI_UNIT_CAPI_DEBUG) // non-template kernel: defined in ONE translation unit (mppi_capi_debug.hip)
 __global__ void k_mlp_step_ref(const DevConsts *__restrict__ C, const MlpDev *__restrict__ M,
                                const float *__restrict__ x, int kx, const float *__restrict__ v, int k,
-                               float *__restrict__ scratch, float *__restrict__ out_next)
+                               float *__restrict__ scratch, float *__restrict__ out_next, int member_stride)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= k) return;
+    M += (size_t)i * member_stride; // 0: one network for every row; 1: row i through the network of member i (a learned batch as its own plant)
     const int s = C->s, a = C->a, nin = s + a;
     float *cur = scratch + (size_t)i * 2 * kHid, *nxt = cur + kHid;
     const float *xi = x + (size_t)(kx == 1 ? 0 : i) * s;

@@ -245,7 +245,10 @@ class LearnerBase:
         """What each member of `batch` is worth as a controller's model: every member's network, with this learner's model's normalisation,
         goes into the B learned controllers `controller` (BatchHandle.learned of B = batch.B members; load_learners), which then run ONE
         closed-loop episode of n_steps steps on the true vehicle `plant` (a Handle, or B of them) from x0 [s] or [B, s], from a zero sequence
-        and step counter 0 -> the summed state cost of each member's episode, C.sum(0), [B]. goals: [n_steps, s] or [n_steps, B, s]."""
+        and step counter 0 -> the summed state cost of each member's episode, C.sum(0), [B]. goals: [n_steps, s] or [n_steps, B, s].
+        `batch` is a LearnerBatch or a WideLearnerBatch: for an NNPointMassModel, narrow or wide, `controller` is
+        BatchHandle.learned(B, ..., model="mlp", a_dim=). k_fold_validation(episode=) and grid_search(by="episode") reach this for narrow
+        models only (they refuse a wide one); for the [in, 256, 256, out] network call episode_fold directly on the WideLearnerBatch."""
         B = batch.B
         controller.load_learners(batch, self.model)
         controller.set_action_sequences(np.zeros((B, controller.tau, controller.a), np.float32))

@@ -16,7 +16,10 @@ BatchHandle's shared keywords only, so the tool also runs on a package without p
 H = 32, B in {8, 32, 128}: the batch; B lone DEFAULT handles stepped one after another on one stream (what a user does without the batch);
 the same B handles on B streams; and the batch's rollout kernel time (its own dispatch timestamps) with B distinct networks against B
 members sharing ONE network. --only batch|shared|serial|streams times one alone (a counter or kernel-trace run).
-    tools/time_batch.py --model nnauv|nnspeed [--hid 16|32] [--layers 1..3] [--shape B,K,H] [--only ...] [--steps N] [--reps R]"""
+    tools/time_batch.py --model nnauv|nnspeed [--hid 16|32] [--layers 1..3] [--shape B,K,H] [--only ...] [--steps N] [--reps R]
+--model mlp|mlp32|mlp16 [--layers 1..3]: the same four figures for the learned point mass (BatchHandle.learned(model="mlp")):
+mlp the [3a, 256, 256, 2a] network (k_rollout_mlp2_batch against lone handles on k_rollout_mlp2), mlp32 / mlp16 Dense(32) / Dense(16) x
+--layers (k_rollout_mlp_small_batch against lone DEFAULT handles: k_rollout_mlp32_pc / k_rollout_mlp_small), at a = 3."""
 import argparse
 import os
 import sys
@@ -103,10 +106,11 @@ def shape(B, K, H, a, steps, reps, only=None, model="pm"):
     return med
 
 
-def learned_net(model, hid, layers, seed):
-    """a random network of the learned 13-state model's shape with a normalisation (what the tests use)"""
+def learned_net(model, hid, layers, seed, a=3):
+    """a random network of the learned model's shape with a normalisation (what the tests use)"""
     rng = np.random.default_rng(seed)
-    dims = [16 if model == "nnauv" else 15] + [hid] * layers + [13 if model == "nnauv" else 6]
+    ends = (3 * a, 2 * a) if model == "mlp" else (16, 13) if model == "nnauv" else (15, 6)
+    dims = [ends[0]] + [hid] * layers + [ends[1]]
     W = [(rng.uniform(-1, 1, (dims[i], dims[i + 1])) / np.sqrt(dims[i])).astype(np.float32) for i in range(layers + 1)]
     b = [(rng.uniform(-1, 1, dims[i + 1]) / np.sqrt(dims[i])).astype(np.float32) for i in range(layers + 1)]
     W[-1] *= 0.1
@@ -115,20 +119,26 @@ def learned_net(model, hid, layers, seed):
                 ymean=rng.uniform(-0.01, 0.01, dims[-1]).astype(np.float32), ystd=rng.uniform(0.8, 1.2, dims[-1]).astype(np.float32))
 
 
-def learned(B, K, H, model, hid, layers, steps, reps, only=None):
+def learned(B, K, H, model, hid, layers, steps, reps, only=None, a=3):
     """one network per member: the batch (distinct networks / one shared network) against B lone default handles, serially and on B streams"""
-    kind = "nnauv" if model == "nnauv" else "nnauv_speed"
-    c = dict(k=K, tau=H, dt=0.1, lam=1.0, sigma=0.25 * np.eye(6), goal=[1.0, 2.0, -3.0, 0, 0, np.sin(0.2), np.cos(0.2)] + [0.0] * 6,
-             Q=np.array([10.0] * 3 + [5.0] * 4 + [1.0] * 6))
-    nets = [learned_net(model, hid, layers, 100 + i) for i in range(B)]
-    x0 = np.array([0.5, -0.5, 0.2, 0.0, 0.0, 0.0, 1.0, 0.3, 0.0, -0.1, 0.0, 0.05, 0.0], np.float32)
+    if model.startswith("mlp"):  # the learned point mass
+        kind, s, net_kw, ctl_kw = "mlp", 2 * a, "mlp", dict(a_dim=a)
+        c = dict(k=K, tau=H, dt=0.1, lam=1.0, sigma=0.25 * np.eye(a), goal=GOAL[:s], Q=np.array([10.0, 1.0] * a))
+        x0 = np.array([0.1, 0, -0.2, 0, 0.3, 0, 0.05, 0][:s], np.float32)
+    else:
+        kind, s, a, ctl_kw = "nnauv" if model == "nnauv" else "nnauv_speed", 13, 6, {}
+        net_kw = kind
+        c = dict(k=K, tau=H, dt=0.1, lam=1.0, sigma=0.25 * np.eye(6), goal=[1.0, 2.0, -3.0, 0, 0, np.sin(0.2), np.cos(0.2)] + [0.0] * 6,
+                 Q=np.array([10.0] * 3 + [5.0] * 4 + [1.0] * 6))
+        x0 = np.array([0.5, -0.5, 0.2, 0.0, 0.0, 0.0, 1.0, 0.3, 0.0, -0.1, 0.0, 0.05, 0.0], np.float32)
+    nets = [learned_net(kind if kind == "mlp" else model, hid, layers, 100 + i, a) for i in range(B)]
     seeds = [1 + i for i in range(B)]
     want = (lambda k: only in (None, k))
-    hb = m.BatchHandle.learned(B, nets, kind, seeds=seeds, **c) if want("batch") else None
-    hsh = m.BatchHandle.learned(B, nets[0], kind, seeds=seeds, **c) if want("shared") else None
-    hs = [m.Handle(seed=seeds[i], s_dim=13, a_dim=6, **{kind: nets[i]}, **c) for i in range(B)] if (want("serial") or want("streams")) else []
-    xb, ub = torch.from_numpy(np.tile(x0, (B, 1))).cuda(), torch.zeros((B, 6), device="cuda")
-    xs, us = [torch.from_numpy(x0.copy()).cuda() for _ in hs], [torch.zeros(6, device="cuda") for _ in hs]
+    hb = m.BatchHandle.learned(B, nets, kind, seeds=seeds, **ctl_kw, **c) if want("batch") else None
+    hsh = m.BatchHandle.learned(B, nets[0], kind, seeds=seeds, **ctl_kw, **c) if want("shared") else None
+    hs = [m.Handle(seed=seeds[i], s_dim=s, a_dim=a, **{net_kw: nets[i]}, **c) for i in range(B)] if (want("serial") or want("streams")) else []
+    xb, ub = torch.from_numpy(np.tile(x0, (B, 1))).cuda(), torch.zeros((B, a), device="cuda")
+    xs, us = [torch.from_numpy(x0.copy()).cuda() for _ in hs], [torch.zeros(a, device="cuda") for _ in hs]
     one = torch.cuda.Stream()
     torch.cuda.synchronize()
     names = dict(batch=hb.rollout_kernel_name() if hb else None, lone=hs[0].rollout_kernel_name() if hs else None)
@@ -234,8 +244,9 @@ def main():
     ap.add_argument("--only", choices=("batch", "streams", "single", "sweep", "uniform", "shared", "serial"),
                     help="time one of the three alone (--sweep: the sweep or the uniform batch alone)")
     ap.add_argument("--sweep", action="store_true", help="a per-member parameter sweep against the uniform batch of the same shape")
-    ap.add_argument("--model", choices=("pm", "auv", "nnauv", "nnspeed"), default="pm",
-                    help="pm: the point mass; auv: the Fossen AUV at the reference's task; nnauv / nnspeed: the learned 13-state models, one network per member")
+    ap.add_argument("--model", choices=("pm", "auv", "nnauv", "nnspeed", "mlp", "mlp32", "mlp16"), default="pm",
+                    help="pm: the point mass; auv: the Fossen AUV at the reference's task; nnauv / nnspeed: the learned 13-state models, one network "
+                         "per member; mlp / mlp32 / mlp16: the learned point mass (2 x 256, Dense(32), Dense(16)), one network per member")
     ap.add_argument("--hid", type=int, choices=(16, 32), default=32, help="nnauv / nnspeed: the hidden width")
     ap.add_argument("--layers", type=int, choices=(1, 2, 3), default=3, help="nnauv / nnspeed: hidden layers")
     ap.add_argument("--shape", help="one shape only: B,K,H (the action dimension: 2 for pm, 6 for auv)")
@@ -243,7 +254,9 @@ def main():
     o = ap.parse_args()
     if o.sweep:
         return main_sweep(o)
-    if o.model in ("nnauv", "nnspeed"):
+    if o.model in ("nnauv", "nnspeed", "mlp", "mlp32", "mlp16"):
+        if o.model.startswith("mlp"):
+            o.hid, o.layers = {"mlp": (256, 2), "mlp32": (32, o.layers), "mlp16": (16, o.layers)}[o.model]
         shapes = [(B, 1024, 32) for B in (8, 32, 128)]
         if o.shape:
             shapes = [tuple(int(v) for v in o.shape.split(","))]

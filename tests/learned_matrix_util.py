@@ -1,0 +1,606 @@
+"""What the learned-model instance-matrix tests share (test_learned_matrix_oracle.py on the CPU, test_learned_matrix_gpu.py on the GPU): a
+restatement in Python of the rules that pick a learned-model rollout kernel instance (mppi_create's mlp_small / mlp_bx3 / mlp_v2 / nb_mlp,
+mppi_set_tuning's mlp_v1 / mlp32_valu / pc_balance, pick_mlp, pick_batch_mlp, pick_gen with its fast_mode, pick_batch_nn, mppi_with_diag,
+mppi_two_tile_balance), the enumeration of the instances a caller can reach, the matrix of cases that launches each of them at its
+kernel's edge shapes, and the oracle side of a case. A plain module in the manner of pc_matrix_util.py; nothing here touches a GPU.
+
+An instance is a tuple (family, template arguments...), the families and their arguments in FAMILIES: ("mlp2", A, DIAG, SRC) is
+k_rollout_mlp2<A, DIAG, SRC>, ("gen", MODEL, W, DIAG) is k_rollout_gen<MODEL, W, DIAG>, and so on. An instance whose noise source is a
+template argument (k_rollout_mlp2, k_rollout_mlp_bx3) counts once per source: rollout_kernel_name() names the Philox one, and the
+injected-noise instance that next_with_noise launches (always the dense-Sigma arithmetic) is named from the restated rule.
+
+A configuration (`cfg`) is a dict of what a caller chooses: kind ("pm": the learned point mass, "nnauv": NNAUVModel, "nnspeed":
+NNAUVModelSpeed), a (pm: 1..4; the 13-state models have a = 6), hid and nh (hidden width, hidden layers), dense (the Sigma form), bx3
+(MPPI_FLAG_MLP_BF16X3), tuning (mlp_v1, mlp32_valu, pc_balance), normalize, batch. A case (`spec`) is a configuration with its shape (K, H),
+its Philox key, its member number (goal, Sigma scale and network differ per member) and the multiplier of the lambda rule.
+
+Every case's lambda comes from the fp64 oracle (lam_of, pc_matrix_util.lam_of's rule): float32(mult x (c_sorted[8] - c_min)) over the costs
+of the case's first step at lambda = 1 (with normalizeCost: over the normalised costs), on the oracle's restatement of the noise.
+tests/test_learned_matrix_oracle.py proves on the CPU that every K = 160 case is then well conditioned in fp32, has no sample that holds
+the weight alone and needs every tile, and that no sample's cost lies so near zero that a bar relative to it would judge the case (cost_cond_max).
+
+The 13-state cases take the diagonal quadratic state cost that test_learned_13_state_kernels_with_ragged_tiles uses.
+"""
+import functools
+import itertools
+import re
+
+import numpy as np
+
+import pc_matrix_util as pm
+from episode_util import make_nnauv
+from oracle import oracle as orc
+
+F32 = np.float32
+N_CU = 256                   # compute units of an MI355X (mppi_handle::n_cu): the tile walkers' grid, the two-tile pipelines' balance
+TILE = 64                    # kMlpR = kMlp2R = kBx3R = kMlp32R = 64 rollouts per tile; the 13-state kernels: R = 64 (mppi_create)
+K = 160                      # three tiles, the last half full; two workgroups of a two-tile pipeline, the second without a second tile
+STEPS = 2                    # fused Philox steps per case: step counters 0 and 1, both halves of the sequence buffer
+INJECTED_STEP = 2            # the lone cases' third step takes the oracle's restatement of the noise of this counter through next_with_noise
+HORIZONS = (1, 4, 5, 9)      # no loop iteration; one whole Philox group (4 steps); ragged groups
+EDGE_H = 5                   # the horizon of the further small shapes
+BIG_H = 2                    # ... and of the large ones
+MULT = 3.0
+COND_FRACTION = 4            # (a) the fp32 oracle's U' within bar / 4 of the fp64 oracle's
+W_MAX = pm.W_MAX             # (b)
+TILE_MIN = pm.TILE_MIN       # (c) 50 x 1e-5
+B = 3                        # members of a batched case
+SRC_PHILOX, SRC_HBM = 0, 1   # NoiseSrc
+MODE_ROLLOUT, MODE_COSTS_GIVEN, MODE_COST_ONLY = 0, 1, 2
+GEN_MODEL = {"nnauv": 1, "nnspeed": 2}   # GEN_MODEL_NNAUV, GEN_MODEL_NNAUV_SPEED (0: the Fossen model, not learned)
+NET_IO = {"nnauv": (16, 13), "nnspeed": (15, 6)}
+# The 13-state goal: the attitude of tests/test_auv_gpu.py's, the position 0.5 m from the start instead of 4 m. At (1, 2, -3) every step costs ~170
+# against a lambda of ~2 by the rule, and the fp32 oracle's U' is 2.5e-6 .. 1.4e-5 from the fp64 oracle's: 39 of the 99 13-state cases broke
+# condition (a), whatever the seed. Next to the start the worst (a) is 7.7e-7.
+GOAL13 = np.array([0.9, -0.8, 0.4, 0.0, 0.0, np.sin(0.2), np.cos(0.2)] + [0.0] * 6)
+X13 = np.array([0.5, -0.5, 0.2, 0.0, 0.0, 0.0, 1.0, 0.3, 0.0, -0.1, 0.0, 0.05, 0.0])
+Q13 = np.array([10.0] * 3 + [5.0] * 4 + [1.0] * 6)
+DENSE_SIGMA6 = (0.25 * np.eye(6) + 0.03 * np.add.outer(np.arange(6), np.arange(6)) / 5.0).astype(F32)   # tests/test_auv_gpu.py
+SCALES = (1.0, 1.2, 0.8)     # member i's Sigma is SCALES[i] x the case's
+# a case that broke a condition gets another seed or multiplier here (never another bar): problem key -> dict(seed=, mult=)
+ADJUST = {
+    # H = 1 at a = 1: U' is ONE number, and the smallest of the nine moves (three tiles left out, three steps) is by chance near zero
+    "pm_a1_256x2_diag_K160_H1_m0": dict(seed=61070),   # (c) 2.26e-4 with the first seed
+    # ... and here the nine smallest costs of the first step lie within 7.5e-5 of each other, so the rule gives lambda = 2.2e-4
+    "pm_a1_32x1_diag_K160_H1_m2": dict(seed=61720),    # (a) 5.21e-6 (b) 0.332 (c) 1.39e-6 with the first seed
+    # one sample's cost lands at 2e-4 among costs of ~10 (the signed action cost cancels the state cost): the fp32 oracle is 2.6e-4 relative away
+    "pm_a1_256x2_diag_K160_H9_m1": dict(seed=61426),   # (d) 2.6e-4 with the first seed
+}
+
+# family -> (kernel, template arguments: i = int, b = bool, what the family is counted under)
+FAMILIES = {
+    "mlp": ("k_rollout_mlp", "ib", "lone point mass"), "mlp2": ("k_rollout_mlp2", "ibi", "lone point mass"),
+    "bx3": ("k_rollout_mlp_bx3", "ibi", "lone point mass"), "mlp32": ("k_rollout_mlp32", "i", "lone point mass"),
+    "mlp32_bx3": ("k_rollout_mlp32_bx3", "i", "lone point mass"), "mlp32_pc": ("k_rollout_mlp32_pc", "ib", "lone point mass"),
+    "small": ("k_rollout_mlp_small", "ii", "lone point mass"),
+    "mlp2_batch": ("k_rollout_mlp2_batch", "ib", "batched point mass"), "small_batch": ("k_rollout_mlp_small_batch", "ii", "batched point mass"),
+    "nnauv32": ("k_rollout_nnauv32", "b", "lone 13-state"), "nnauv32_bx3": ("k_rollout_nnauv32_bx3", "b", "lone 13-state"),
+    "nnauv_pc": ("k_rollout_nnauv_pc", "b", "lone 13-state"), "nnspeed32": ("k_rollout_nnspeed32", "ib", "lone 13-state"),
+    "nnspeed_pc": ("k_rollout_nnspeed_pc", "ib", "lone 13-state"), "gen": ("k_rollout_gen", "iib", "lone 13-state"),
+    "nn_batch": ("k_rollout_nn_batch", "iib", "batched 13-state"),
+}
+COUNTED = ("lone point mass", "batched point mass", "lone 13-state", "batched 13-state")
+PIPELINES = ("mlp32_pc", "nnauv_pc", "nnspeed_pc")                                  # two tiles per workgroup, roles by SIMD
+TWO_SETS = ("mlp2", "bx3", "mlp32", "mlp32_bx3", "nnauv32", "nnauv32_bx3", "nnspeed32")   # a tile owned as two sets of 32 rollouts
+ONE_WAVE = ("small", "gen")                                                         # one wave = one 64-rollout tile
+WALKERS = ("mlp2", "bx3")                                                           # min(nb, n_cu) workgroups walk the tiles
+SPLIT_BF16 = ("bx3", "mlp32_bx3", "nnauv32_bx3")
+
+
+class Refused(Exception):
+    """the library refuses the configuration (mppi_create, mppi_create_batch_*, mppi_set_tuning)"""
+
+
+# ---- the creation and tuning rules, restated ---------------------------------------------------------------------------------------------
+def tiles(k):
+    """nb_mlp (kMlpR = kMlp2R = 64) and the 13-state nb (R = 64)"""
+    return (k + TILE - 1) // TILE
+
+
+def is_diag(cfg):
+    """mppi_with_diag: a 1 x 1 Sigma is always diagonal"""
+    return (cfg["kind"] == "pm" and cfg["a"] == 1) or not cfg.get("dense")
+
+
+def create(cfg):
+    """mppi_create (a batch: mppi_create_batch_mlp / _learned on top) and mppi_set_tuning -> the handle's switches
+    dict(small, bx3, v2, valu, balance) or Refused"""
+    kind, hid, nh, bx3, batch = cfg["kind"], cfg["hid"], cfg.get("nh", 2), bool(cfg.get("bx3")), bool(cfg.get("batch"))
+    if kind == "pm":
+        if not 1 <= cfg["a"] <= 4:
+            raise Refused("MLP rollouts are instantiated for a_dim <= 4")
+        big, small = hid == 256 and nh == 2, hid in (16, 32) and 1 <= nh <= 3
+        if not big and not small:
+            raise Refused("MLP kernels exist for hidden widths {256,256} and 1-3 equal hidden layers of 16 or 32")
+    else:
+        if kind == "nnspeed" and bx3:
+            raise Refused("no split-bf16 kernel for NNAUVModelSpeed")
+        if hid not in (16, 32) or not 1 <= nh <= 3:
+            raise Refused("NNAUVModel kernels exist for 1-3 equal hidden layers of 16 or 32")
+    if bx3 and hid == 16:
+        raise Refused("MPPI_FLAG_MLP_BF16X3 applies to the 256-wide and the 32-wide networks")
+    st = dict(small=0 if (kind == "pm" and hid == 256) else hid, bx3=int(bx3 and kind in ("pm", "nnauv")), valu=0, balance=1)
+    st["v2"] = int(kind == "pm" and not st["small"] and not st["bx3"] and cfg["a"] <= 3)
+    if batch:
+        if bx3 or cfg.get("normalize"):
+            raise Refused("a batch of learned controllers takes neither MPPI_FLAG_MLP_BF16X3 nor normalize_cost")
+        if kind == "pm" and not st["small"] and not st["v2"]:
+            raise Refused("batched MLP controllers: the {256, 256} network at a_dim = 4 is not supported")
+    for key, value in (cfg.get("tuning") or {}).items():
+        if key == "mlp_v1":
+            if batch and value:
+                raise Refused("tuning mlp_v1: a batched handle always runs the two-launch batched step")
+            if kind != "pm" or st["bx3"] or st["small"]:
+                raise Refused("not an exact-fp32 2x256 MLP handle")
+            st["v2"] = int(value == 0 and cfg["a"] <= 3)
+        elif key == "mlp32_valu":
+            if batch and value:
+                raise Refused("tuning mlp32_valu: a batched handle always runs the two-launch batched step")
+            if not (st["small"] == 32 or (kind == "nnspeed" and st["small"] == 16)) or st["bx3"] or not 0 <= value <= 2:
+                raise Refused("not an exact-fp32 Dense(32) MLP handle (or an NNAUVModelSpeed one)")
+            st["valu"] = value
+        elif key == "pc_balance":
+            st["balance"] = int(value != 0)
+        else:
+            raise KeyError(key)
+    return st
+
+
+def two_tile_balance(st, wgs, n_cu=N_CU):
+    """mppi_two_tile_balance: the roles follow the SIMD only within two rounds of the chip and unless tuned off"""
+    return int(wgs <= 2 * n_cu and bool(st["balance"]))
+
+
+# ---- the pick rules, restated: -> (instance, workgroups) ---------------------------------------------------------------------------------
+def pick_mlp(cfg, st, src, k, n_cu=N_CU):
+    a, nb, d = cfg["a"], tiles(k), is_diag(cfg)
+    if st["small"] == 32 and st["bx3"]:
+        return ("mlp32_bx3", a), nb
+    if st["small"] == 32 and st["valu"] == 0:
+        return ("mlp32_pc", a, d), (nb + 1) // 2
+    if st["small"] == 32 and st["valu"] == 2:
+        return ("mlp32", a), nb
+    if st["small"]:
+        return ("small", a, st["small"]), nb
+    by_src = d if src == SRC_PHILOX else False  # injected noise runs one instance, the dense-Sigma arithmetic
+    if st["bx3"]:
+        return ("bx3", a, by_src, src), min(nb, n_cu)
+    if st["v2"]:
+        return ("mlp2", a, by_src, src), min(nb, n_cu)
+    return ("mlp", a, d), nb
+
+
+def pick_batch_mlp(cfg, st, k, n_cu=N_CU):
+    a, nb = cfg["a"], tiles(k)
+    if st["small"]:
+        return ("small_batch", a, st["small"]), nb * B
+    assert st["v2"] and a <= 3
+    return ("mlp2_batch", a, is_diag(cfg)), min(nb, n_cu) * B
+
+
+def pick_gen(cfg, st, mode, noise_out, k):
+    kind, d, nb = cfg["kind"], is_diag(cfg), tiles(k)
+    wgs = (nb + 1) // 2
+    fast_mode = mode in (MODE_ROLLOUT, MODE_COST_ONLY) and not noise_out  # a noise export and MODE_COSTS_GIVEN fall to k_rollout_gen
+    if kind == "nnauv" and st["small"] == 32 and st["valu"] != 1 and fast_mode:
+        if st["bx3"]:
+            return ("nnauv32_bx3", d), nb
+        if st["valu"] == 0:
+            return ("nnauv_pc", d), wgs
+        return ("nnauv32", d), nb
+    if kind == "nnspeed" and st["valu"] != 1 and fast_mode:
+        if st["valu"] == 2:
+            return ("nnspeed32", st["small"], d), nb
+        return ("nnspeed_pc", st["small"], d), wgs
+    return ("gen", GEN_MODEL[kind], st["small"], d), nb
+
+
+def pick_batch_nn(cfg, st, k):
+    return ("nn_batch", GEN_MODEL[cfg["kind"]], st["small"], is_diag(cfg)), tiles(k) * B
+
+
+def route(cfg, call="next", k=K, n_cu=N_CU, grids=False):
+    """the learned-model instances one control step launches, in order. call: "next" (the fused Philox step) or "noise" (next_with_noise).
+    A normalizeCost step is the cost-only pass of the handle's kernel, k_cost_normalize, then the records from the given costs: on the tile
+    kernel for the point mass (("tile", A): not a learned kernel), on k_rollout_gen for the 13-state models. grids: -> [(instance, workgroups)]"""
+    st = create(cfg)
+    src = SRC_PHILOX if call == "next" else SRC_HBM
+    if cfg.get("batch"):
+        assert call == "next"
+        out = [pick_batch_mlp(cfg, st, k, n_cu) if cfg["kind"] == "pm" else pick_batch_nn(cfg, st, k)]
+    elif cfg["kind"] == "pm":
+        out = [pick_mlp(cfg, st, src, k, n_cu)]
+        if cfg.get("normalize"):
+            out.append((("tile", cfg["a"]), tiles(k)))
+    elif cfg.get("normalize"):
+        out = [pick_gen(cfg, st, MODE_COST_ONLY, False, k), pick_gen(cfg, st, MODE_COSTS_GIVEN, False, k)]
+    else:
+        out = [pick_gen(cfg, st, MODE_ROLLOUT, False, k)]
+    return out if grids else [i for i, _ in out]
+
+
+def fmt(inst):
+    """the instance's name as rollout_kernel_name() gives it"""
+    args = ", ".join(("true" if v else "false") if isinstance(v, bool) else "%d" % v for v in inst[1:])
+    return "mppi::%s<%s>" % (FAMILIES[inst[0]][0], args)
+
+
+def expected_name(cfg):
+    """what rollout_kernel_name() must return: the Philox step's rollout launch (normalizeCost: its cost-only pass)"""
+    return fmt(route(cfg)[0])
+
+
+@functools.lru_cache(None)
+def reachable_instances():
+    """every learned-model instance some configuration reaches, by walking the configuration space through route()"""
+    out = set()
+    for kind, a, (hid, nh), bx3, dense, v1, valu, batch, norm in itertools.product(
+            ("pm", "nnauv", "nnspeed"), (1, 2, 3, 4), ((256, 2), (64, 2), (32, 3), (16, 1)), (False, True), (False, True), (None, 0, 1),
+            (None, 0, 1, 2), (False, True), (False, True)):
+        if kind != "pm" and a != 1:
+            continue
+        tuning = {k_: v for k_, v in (("mlp_v1", v1), ("mlp32_valu", valu)) if v is not None}
+        cfg = dict(kind=kind, a=a if kind == "pm" else 6, hid=hid, nh=nh, bx3=bx3, dense=dense, tuning=tuning, batch=batch, normalize=norm)
+        for call in ("next",) if batch else ("next", "noise"):
+            try:
+                out.update(i for i in route(cfg, call) if i[0] != "tile")
+            except Refused:
+                pass
+    return frozenset(out)
+
+
+def family_count(insts, group):
+    return sum(1 for i in insts if FAMILIES[i[0]][2] == group)
+
+
+# ---- the matrix --------------------------------------------------------------------------------------------------------------------------
+def spec(kind, hid, nh, a=6, dense=False, bx3=False, tuning=None, normalize=False, k=K, H=EDGE_H, member=0, batch=False):
+    """one case: a configuration + its shape, member number, Philox key and lambda multiplier"""
+    c = dict(kind=kind, a=a, hid=hid, nh=nh, dense=bool(dense), bx3=bool(bx3), tuning=dict(tuning or {}), normalize=bool(normalize), K=k, H=H,
+             member=member, batch=bool(batch), mult=MULT)
+    c["seed"] = 20000 + 1000 * a + 7 * H + 300 * member + (1 if dense else 0) + (50 if hid == 32 else 100 if hid == 16 else 0) + k % 97
+    c["key"] = problem_key(c)
+    tune = "".join("_%s%d" % (t.replace("mlp32_", "").replace("mlp_", "").replace("pc_", ""), v) for t, v in sorted(c["tuning"].items()))
+    c["id"] = c["key"] + ("_bx3" if bx3 else "") + tune
+    c.update(ADJUST.get(c["key"], {}))
+    return c
+
+
+def problem_key(c):
+    """what the oracle's problem (and hence lambda and the conditions) depends on: not the kernel the handle is tuned onto"""
+    return "%s_a%d_%dx%d_%s%s_K%d_H%d_m%d" % (c["kind"], c["a"], c["hid"], c["nh"], "dsig" if c["dense"] else "diag", "_norm" if c["normalize"] else "",
+                                              c["K"], c["H"], c["member"])
+
+
+def cfg_of(c, batch=None):
+    return dict(kind=c["kind"], a=c["a"], hid=c["hid"], nh=c["nh"], dense=c["dense"], bx3=c["bx3"], tuning=c["tuning"], normalize=c["normalize"],
+                batch=c["batch"] if batch is None else batch)
+
+
+def depth(H):
+    """hidden layers by horizon, so that every depth the kernels loop over (1..3) runs in every family"""
+    return {1: 1, 2: 2, 4: 3, 5: 2, 9: 3}[H]
+
+
+def sigmas(a):
+    return [False] if a == 1 else [False, True]
+
+
+# how a lone handle is brought onto each kernel family: family -> (kind, [hidden widths], bx3, tuning, action dimensions)
+LONE = {
+    "mlp2": ("pm", [256], False, {}, (1, 2, 3)),                       # mlp_v2: a <= 3
+    "mlp": ("pm", [256], False, {"mlp_v1": 1}, (1, 2, 3, 4)),         # the default at a = 4, mlp_v1 = 1 below
+    "bx3": ("pm", [256], True, {}, (1, 2, 3, 4)),
+    "mlp32_pc": ("pm", [32], False, {}, (1, 2, 3, 4)),                # mlp32_valu = 0
+    "mlp32": ("pm", [32], False, {"mlp32_valu": 2}, (1, 2, 3, 4)),
+    "mlp32_bx3": ("pm", [32], True, {}, (1, 2, 3, 4)),
+    "small": ("pm", [16, 32], False, {"mlp32_valu": 1}, (1, 2, 3, 4)),   # Dense(16): the default, no tuning
+    "nnauv_pc": ("nnauv", [32], False, {}, (6,)),
+    "nnauv32": ("nnauv", [32], False, {"mlp32_valu": 2}, (6,)),
+    "nnauv32_bx3": ("nnauv", [32], True, {}, (6,)),
+    "gen_nnauv": ("nnauv", [16, 32], False, {"mlp32_valu": 1}, (6,)),  # Dense(16): the default
+    "nnspeed_pc": ("nnspeed", [16, 32], False, {}, (6,)),
+    "nnspeed32": ("nnspeed", [16, 32], False, {"mlp32_valu": 2}, (6,)),
+    "gen_nnspeed": ("nnspeed", [16, 32], False, {"mlp32_valu": 1}, (6,)),
+}
+# the batched families: family -> (kind, [hidden widths], action dimensions)
+BATCHED = {"mlp2_batch": ("pm", [256], (1, 2, 3)), "small_batch": ("pm", [16, 32], (1, 2, 3, 4)), "nn_batch_nnauv": ("nnauv", [16, 32], (6,)),
+           "nn_batch_nnspeed": ("nnspeed", [16, 32], (6,))}
+
+
+def kernel_family(group_family):
+    return "gen" if group_family.startswith("gen_") else "nn_batch" if group_family.startswith("nn_batch") else group_family
+
+
+def lone_tuning(fam, kind, hid):
+    """the tuning that brings a handle of this network onto the family (none where the family is the network's default)"""
+    t = dict(LONE[fam][3])
+    if "mlp32_valu" in t and t["mlp32_valu"] == 1 and hid == 16 and kind != "nnspeed":
+        t = {}  # Dense(16) runs the one-wave kernel by default (and takes no mlp32_valu), except NNAUVModelSpeed's
+    return t
+
+
+def lone_groups():
+    """(family, action dimension): one GPU test each"""
+    return [(fam, a) for fam, v in LONE.items() for a in v[4]]
+
+
+def batch_groups():
+    return [(fam, a) for fam, v in BATCHED.items() for a in v[2]]
+
+
+def group_id(g):
+    return "%s_a%d" % g
+
+
+def extra_shapes(fam):
+    """the further small shapes of a family, each from a constant of its kernel: [(K, why)]"""
+    kf = kernel_family(fam)
+    if kf in TWO_SETS or kf == "mlp":
+        # kMlp2R / kBx3R / kMlp32R = 64 as two sets of 32 (k_rollout_mlp: kMlpR = 64 over 8 waves)
+        return [(33, "set B holds one lane"), (65, "a second tile whose set B is all clamped lanes")]
+    if kf in ONE_WAVE:
+        return [(1, "one lane of one wave"), (65, "a second tile of one lane")]       # 64 lanes = one tile
+    return [(64, "one tile, one workgroup: the workgroup's second tile is missing")]     # the pipelines: two tiles per workgroup
+
+
+def lone_cases(fam, a):
+    """every (hidden width, Sigma form) of the family at this action dimension: K = 160 at the edge horizons, then the further shapes"""
+    kind, hids, bx3, _, _ = LONE[fam]
+    out = []
+    for hid in hids:
+        for dense in ([False, True] if kind != "pm" else sigmas(a)):
+            kw = dict(a=a, dense=dense, bx3=bx3, tuning=lone_tuning(fam, kind, hid))
+            out += [spec(kind, hid, 2 if hid == 256 else depth(H), H=H, **kw) for H in HORIZONS]
+            for k, _ in extra_shapes(fam):
+                H = BIG_H if kernel_family(fam) in PIPELINES else EDGE_H
+                out.append(spec(kind, hid, 2 if hid == 256 else depth(H), k=k, H=H, **kw))
+    return out
+
+
+def normalize_cases():
+    """normalizeCost: one case per kernel family (MODE_COST_ONLY of the learned kernel, k_cost_normalize, the records from the given costs)"""
+    out = []
+    for fam, (kind, hids, bx3, _, dims) in LONE.items():
+        a, hid = (4 if fam == "mlp" else 3) if kind == "pm" else 6, hids[-1]
+        out.append((fam, spec(kind, hid, 2 if hid == 256 else 3, a=a, dense=fam in ("mlp32_pc", "nnspeed32"), bx3=bx3,
+                              tuning={} if fam == "mlp" else lone_tuning(fam, kind, hid), normalize=True, H=EDGE_H)))
+    return out
+
+
+def big_cases():
+    """the two-tile pipelines beyond one round of roles, one instance each at H = 2: workgroups past 255 (blockIdx.x >> 8: the roles swap),
+    then 513 workgroups (mppi_two_tile_balance: off above 2 x n_cu); the tile walkers with one tile more than there are CUs"""
+    out = []
+    for fam, hid, dense in (("mlp32_pc", 32, True), ("nnauv_pc", 32, False), ("nnspeed_pc", 16, True)):
+        kind = LONE[fam][0]
+        for k in (32768 + 65, 65536 + 1):
+            out.append((fam, spec(kind, hid, 2, a=3 if kind == "pm" else 6, dense=dense, k=k, H=BIG_H)))
+    for fam in WALKERS:  # a = 2: one a other than 3; one oracle problem for both (the 2x256 network at 16385 rollouts is the matrix's dearest)
+        out.append((fam, spec("pm", 256, 2, a=2, dense=True, bx3=(fam == "bx3"), k=TILE * N_CU + 1, H=BIG_H)))
+    return out
+
+
+def balance_cases():
+    """pc_balance = 0 against the default on the three learned pipelines: (family, case)"""
+    out = []
+    for fam, hid in (("mlp32_pc", 32), ("nnauv_pc", 32), ("nnspeed_pc", 32)):
+        kind = LONE[fam][0]
+        for k, H in ((K, EDGE_H), (32768 + 65, BIG_H)):
+            out.append((fam, spec(kind, hid, 2 if H == BIG_H else depth(H), a=3 if kind == "pm" else 6, k=k, H=H)))
+    return out
+
+
+def batch_cases(fam, a):
+    """every (hidden width, Sigma form) of the batched family at K = 160 and the edge horizons: each entry is the B members' lone cases,
+    each with its own network, Philox key, goal, lambda and Sigma scale"""
+    kind, hids, _ = BATCHED[fam]
+    out = []
+    for hid in hids:
+        for dense in ([False, True] if kind != "pm" else sigmas(a)):
+            for H in HORIZONS:
+                tuning = {"mlp32_valu": 1} if (hid == 32 or kind == "nnspeed") else {}  # the lone kernel the batch mirrors (k_rollout_mlp_small / _gen)
+                out.append([spec(kind, hid, 2 if hid == 256 else depth(H), a=a, dense=dense, tuning=tuning, H=H, member=i) for i in range(B)])
+    return out
+
+
+def batch_cfg(members):
+    return dict(cfg_of(members[0], batch=True), tuning={})
+
+
+def calls(c):
+    """the calls a lone case makes: the fused Philox steps, then one step on injected noise"""
+    return ["next"] * STEPS + ["noise"]
+
+
+def matrix_instances():
+    """every instance the GPU file launches, from the restated rules"""
+    out = set()
+    every = [c for g in lone_groups() for c in lone_cases(*g)] + [c for _, c in normalize_cases() + big_cases() + balance_cases()]
+    for c in every:
+        for call in set(calls(c)):
+            out.update(route(cfg_of(c), call, c["K"]))
+    for g in batch_groups():
+        for members in batch_cases(*g):
+            out.update(route(batch_cfg(members), "next", K))
+            for c in members:
+                out.update(route(cfg_of(c), "next", K))
+    return {i for i in out if i[0] != "tile"}
+
+
+def oracle_cases(k=K):
+    """every case of this K (None: every other K) the GPU file compares with the oracle, once per oracle problem: {problem key: case}"""
+    every = [c for g in lone_groups() for c in lone_cases(*g)] + [c for _, c in normalize_cases() + big_cases() + balance_cases()]
+    every += [c for g in batch_groups() for members in batch_cases(*g) for c in members]
+    out = {}
+    for c in every:
+        if (c["K"] == K) == (k == K):
+            out.setdefault(c["key"], c)
+    return out
+
+
+# ---- a case on both sides ----------------------------------------------------------------------------------------------------------------
+def split_bf16(c):
+    return bool(c["bx3"])
+
+
+def u_bar(c):
+    """MLP_VARIANTS' bars on the control update (tests/test_parity_gpu.py)"""
+    return 2e-5 if split_bf16(c) else 1e-5
+
+
+def cost_factor(c):
+    return 8.0 if split_bf16(c) else 4.0
+
+
+def cost_cond_max(c):
+    """(d) the fp32 oracle's sample costs within this of the fp64 oracle's, relative: the costs' bar on the GPU is 2e-5 and factor x the fp32
+    oracle's own distance, so a case is fit to judge a kernel only while the second is the smaller one. (The C++ action cost's
+    lambda u' Sigma^-1 eps is signed: a sample's cost can land next to zero, and a bar relative to it judges the case.)"""
+    return 2e-5 / cost_factor(c)
+
+
+def sigma_of(c):
+    base = (DENSE_SIGMA6 if c["dense"] else 0.25 * np.eye(6)) if c["kind"] != "pm" else (pm.DENSE_SIGMA if c["dense"] else pm.DIAG_SIGMA)[:c["a"], :c["a"]]
+    return np.ascontiguousarray(SCALES[c["member"]] * np.asarray(base, np.float64)).astype(F32)
+
+
+def goal_of(c):
+    rng = np.random.default_rng(900 + c["member"])
+    if c["kind"] != "pm":
+        g = GOAL13.copy()
+        g[:3] += (0.0 if c["member"] == 0 else 1.0) * rng.uniform(-1, 1, 3)
+        return g.astype(F32)
+    g = np.array(pm.GOALS[0][:2 * c["a"]], np.float64)
+    if c["member"]:
+        g[0::2] = rng.uniform(-1, 1, c["a"])
+    return g.astype(F32)
+
+
+def q_of(c):
+    return Q13.astype(F32) if c["kind"] != "pm" else (1.0 + 0.1 * np.arange(2 * c["a"])).astype(F32)
+
+
+@functools.lru_cache(None)
+def _net(kind, a, hid, nh, member):
+    n_in, n_out = (3 * a, 2 * a) if kind == "pm" else NET_IO[kind]
+    return make_nnauv(400 + 31 * a + hid + 5 * nh + 17 * member, hid, nh, n_in, n_out)
+
+
+def net_of(c):
+    """the case's network and normalisation (episode_util.make_nnauv; with 15 inputs and 6 outputs it is what the lone tests' make_nnauv_speed makes)"""
+    return _net(c["kind"], c["a"], c["hid"], c["nh"], c["member"])
+
+
+def inputs(c):
+    """x and the nominal sequence as the learned tests make them: the point mass x = 0.2 randn, the 13-state models the tests' X0 with the
+    position and the velocities moved; U = 0.1 randn"""
+    rng = np.random.default_rng(c["seed"])
+    if c["kind"] == "pm":
+        x = 0.2 * rng.standard_normal(2 * c["a"])
+    else:
+        x = X13.copy()
+        x[:3] += rng.uniform(-0.5, 0.5, 3)
+        x[7:] += rng.uniform(-0.1, 0.1, 6)
+    return x.astype(F32), (0.1 * rng.standard_normal((c["H"], c["a"]))).astype(F32)
+
+
+def model_kw(c):
+    return {"pm": "mlp", "nnauv": "nnauv", "nnspeed": "nnauv_speed"}[c["kind"]]
+
+
+def problem_kw(c, lam):
+    s = 2 * c["a"] if c["kind"] == "pm" else 13
+    return dict(tau=c["H"], s=s, a=c["a"], dt=0.1, lam=lam, sigma=sigma_of(c), goal=goal_of(c), Q=q_of(c), threads=0, **{model_kw(c): net_of(c)})
+
+
+def noise(c, step):
+    return orc.noise(c["seed"], step, 0, c["K"], c["H"], c["a"], sigma_of(c))
+
+
+_LAM = {}
+
+
+def lam_of(c):
+    """float32(mult x (c_sorted[8] - c_min)) over the fp64 oracle's costs of the first step at lambda = 1 (normalizeCost: the normalised
+    costs); fewer than nine samples: the largest gap. One round, as pc_matrix_util.lam_of."""
+    key = (c["key"], c["seed"], c["mult"])
+    if key not in _LAM:
+        x, U = inputs(c)
+        c64 = np.sort(orc.Problem(dtype=np.float64, **problem_kw(c, 1.0)).next_with_noise(x, U, noise(c, 0), normalize=False)[2])
+        gap = c64[min(8, c64.size - 1)] - c64[0]
+        if c64.size == 1:
+            gap = 1.0 / c["mult"]  # one sample holds the weight whatever the temperature
+        if c["normalize"]:
+            gap /= c64[-1] - c64[0]
+        _LAM[key] = float(F32(c["mult"] * gap))
+    return _LAM[key]
+
+
+def make_case(c):
+    """-> dict(handle: m.Handle's keywords, problem: orc.Problem's keywords (no dtype), x, U, lam)"""
+    lam = lam_of(c)
+    x, U = inputs(c)
+    h = dict(k=c["K"], tau=c["H"], s_dim=x.size, a_dim=c["a"], dt=0.1, lam=lam, sigma=sigma_of(c), goal=goal_of(c), Q=q_of(c), seed=c["seed"],
+             tuning=dict(c["tuning"]) or None, **{model_kw(c): net_of(c)})
+    if c["bx3"]:
+        h["mlp_bf16x3"] = True
+    if c["normalize"]:
+        h["normalize_cost"] = True
+    return dict(handle=h, problem=problem_kw(c, lam), x=x, U=U, lam=lam)
+
+
+def problems(mk):
+    return orc.Problem(**mk["problem"]), orc.Problem(dtype=np.float64, **mk["problem"])
+
+
+updated = pm.updated
+softmin = pm.softmin
+
+
+def conditions(c, loo=True):
+    """the conditions of the case over its steps (the Philox steps and the injected one), oracle alone on the restated noise: -> (a) the
+    largest distance of the fp32 oracle's U' from the fp64 oracle's, (b) the largest weight of one sample, (c) the smallest move of the fp64
+    U' when one tile is left out (loo = False, the large shapes: inf), and the largest relative distance of the fp32 oracle's costs from
+    the fp64 oracle's"""
+    mk = make_case(c)
+    p32, p64 = problems(mk)
+    x, U, lam, nrm, k = mk["x"], mk["U"], mk["lam"], c["normalize"], c["K"]
+    cond, wmax, move, rel = 0.0, 0.0, np.inf, 0.0
+    for step in range(STEPS + (0 if c["member"] else 1)):  # (members 1.. run in a batch and on its lone twin: the Philox steps only)
+        eps = noise(c, step)
+        u64, Us64, c64 = p64.next_with_noise(x, U, eps, normalize=nrm)
+        u32, Us32, c32 = p32.next_with_noise(x, U, eps, normalize=nrm)
+        Uupd = updated(u64, Us64)
+        cond = max(cond, float(np.abs(updated(u32, Us32) - Uupd).max()))
+        wmax = max(wmax, float(softmin(c64, lam, nrm).max()))
+        rel = max(rel, float((np.abs(c32 - c64) / np.abs(c64)).max()))
+        for t in range(tiles(k) if loo else 0):
+            rest = np.r_[0:t * TILE, min(k, (t + 1) * TILE):k]
+            Uloo = U.astype(np.float64) + np.tensordot(softmin(c64[rest], lam, nrm), eps[rest].astype(np.float64), axes=(0, 0))
+            move = min(move, float(np.abs(Uloo - Uupd).max()))
+        U = Us32
+    return cond, wmax, move, rel
+
+
+# ---- the library's instances, from its bytes ---------------------------------------------------------------------------------------------
+def compiled_instances(blob):
+    """the learned families' instances in the library's mangled names, e.g. 14k_rollout_mlp2ILi1ELb0ELi1EE (the length in front keeps
+    k_rollout_mlp apart from k_rollout_mlp2)"""
+    out = set()
+    for fam, (kernel, sig, _) in FAMILIES.items():
+        pat = ("%d%sI" % (len(kernel), kernel)).encode() + b"".join(rb"Li(\d+)E" if t == "i" else rb"Lb([01])E" for t in sig) + rb"E"
+        for g in re.findall(pat, blob):
+            g = (g,) if isinstance(g, bytes) else g
+            out.add((fam,) + tuple(int(v) if t == "i" else v == b"1" for v, t in zip(g, sig)))
+    return out
+
+
+def exclusion(inst):
+    """why a compiled instance is not in the matrix (None: it must be)"""
+    fam = inst[0]
+    if fam in ("mlp", "mlp2", "bx3", "mlp32_pc", "mlp2_batch") and inst[1] == 1 and not inst[2] and not (fam in ("mlp2", "bx3") and inst[3] == SRC_HBM):
+        return "unreachable: a 1 x 1 Sigma is always diagonal, a = 1 never takes DIAG = false on the Philox path"
+    if fam == "gen" and inst[1] == 0:
+        return "out of this matrix: k_rollout_gen<GEN_MODEL_AUV, ..> is the Fossen model's one-wave kernel, not a learned model; tests/test_auv_gpu.py holds it"
+    return None

@@ -14,7 +14,8 @@ StaticQuatCost's existing bar (3e-6 relative: device acosf against libm) and the
 tests/test_auv_gpu.py); they run colder than the rest (tests/needle_util.py says why), so eta and w[k*] there are nearly 1 by construction.
 
 Out of scope: the learned-model kernels (k_rollout_mlp*, k_rollout_nnauv*, k_rollout_nnspeed*) — a learned model has no zero-cost rest
-point to build a needle on.
+point to build a needle on; their coverage is the learned-model instance matrix (tests/test_learned_matrix_gpu.py, proven on the CPU by
+tests/test_learned_matrix_oracle.py), which compares every sample's cost at an ordinary temperature.
 """
 import numpy as np
 import pytest

@@ -22,8 +22,8 @@ and the rate with the smallest mean held-out loss trains the model; one more lin
 --hidden 256 the batch is a WideLearnerBatch, the same held-out table for the [in, 256, 256, out] network.
     python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2 --kfold-val
 chooses the rate by what the controller needs instead: every fold's network is rolled H steps open-loop along the windows of the round's
-episode (LearnerBase.validate_fold: all rates x folds in one launch) and the rate with the smallest mean H-step error wins; a second
-line per round shows that table.
+episode (LearnerBase.k_fold_trajectory_validation / validate_fold: all rates x folds in one launch, narrow networks and the --hidden 256
+one alike) and the rate with the smallest mean H-step error wins; a second line per round shows that table.
     python examples/learn_loop.py --kfold 5 --lrs 1e-3,3e-3,1e-2 --kfold-episode
 chooses the rate by what the model is FOR: every fold's network becomes the model of its own controller — rates x folds learned
 controllers in one batch (BatchHandle.learned, one network per member, stepped in the same two launches as one) — and each runs a short
@@ -117,8 +117,12 @@ def run(o):
             # the round's rate by k-fold cross-validation over --lrs: every rate x every fold trains at once, as one batch of learners
             by_val = getattr(o, "kfold_val", False)
             episode = dict(controller=folds_ctl, plant=fossen, x0=x0, n_steps=o.episode_steps) if by_episode else None
-            lr, table = learner.grid_search(o.lrs, k=o.kfold, epoch=o.epochs, val=windows_val(X, U, o.horizon) if by_val else None,
-                                            by="episode" if by_episode else "val" if by_val else "test", episode=episode)
+            if by_val:  # narrow or wide ([in, 256, 256, out]: grid_search(by="val") refuses it): the last validation's table and its argmin
+                log = learner.k_fold_trajectory_validation(k=o.kfold, learningRate=o.lrs, epoch=o.epochs, val=windows_val(X, U, o.horizon))
+                table = log["val"][-1].astype(np.float64).mean(axis=1)
+                lr = o.lrs[int(np.argmin(table))]
+            else:
+                lr, table = learner.grid_search(o.lrs, k=o.kfold, epoch=o.epochs, by="episode" if by_episode else "test", episode=episode)
             held_out = learner.kfold_log["test"][-1].astype(np.float64).mean(axis=1)
             print("round %d: %d-fold held-out loss after %d epochs by learning rate: %s -> lr %g" % (
                 r + 1, o.kfold, o.epochs, ", ".join("%g: %.6g" % (a, b) for a, b in zip(o.lrs, held_out)), lr), flush=True)
@@ -176,8 +180,6 @@ def main(argv=None, on_round=None):
         ap.error("--kfold K and --lrs a,b,c go together")
     if o.kfold and (o.kfold < 2 or o.kfold > o.steps):
         ap.error("--kfold: 2 <= K <= --steps")
-    if o.kfold_val and o.hidden == 256:
-        ap.error("--kfold-val rolls every fold's network: trajectory validation of wide members is not built, not with --hidden 256")
     if o.hidden == 256 and o.model != "point_mass":
         ap.error("--hidden 256 is the point-mass network: use --model point_mass")
     o.on_round = on_round

@@ -727,7 +727,8 @@ mppi_status mppi_learner_batch_rollout(mppi_learner_batch *lb, const mppi_learne
  * interact. Deterministic (no float atomics). A member costs 1.0 MB of weights and moments, 0.33 MB of partial tiles per 512 training rows
  * of the largest split and 4.4 KB of rows, activations and deltas per row of the largest split: a batch too large for the device is MPPI_ERR_ALLOC and the object stays destroyable (and usable
  * after smaller splits). Not thread-safe per object. Errors as the learner's: mppi_learner_wide_batch_last_error(NULL) after a failed create.
- * Out of scope: trajectory validation of a wide batch — mppi_learner_batch_rollout stays narrow-only and has no wide namesake. */
+ * Trajectory validation of a wide batch is mppi_learner_wide_batch_validate below: an entry point of its own — mppi_learner_batch_rollout
+ * stays narrow-only and has no wide namesake. */
 typedef struct mppi_learner_wide_batch mppi_learner_wide_batch;
 mppi_status mppi_learner_wide_batch_create(int n_members, int n_layers /* 3 */, const int32_t *widths /* [4] */, const float *const *W,
                                            const float *const *b, int device, mppi_learner_wide_batch **out);
@@ -746,6 +747,24 @@ mppi_status mppi_learner_wide_batch_train(mppi_learner_wide_batch *wb, int steps
                                           const float *beta2, const float *eps /* each [B] or NULL = 0.9 / 0.999 / 1e-7 */,
                                           float *loss_train /* [steps, B] or NULL */, float *loss_test /* [steps, B] or NULL */);
 mppi_status mppi_learner_wide_batch_evaluate(mppi_learner_wide_batch *wb, float *loss_train /* [B] */, float *loss_test /* [B] */);
+/* ---- trajectory validation of the wide members: mppi_learner_batch_rollout's arguments and meaning for the [3a, 256, 256, 2a] network.
+ * Every member's network, as the MPPI_MODEL_MLP `model` describes it, rolled open-loop along n action sequences of T steps in ONE launch
+ * (k_wb_rollout: vector-ALU fp32 in the plain order, not the learner's matrix-core tiles) on the batch's stream, behind any training in
+ * flight; one synchronisation at the end. Host pointers.
+ *   X_out[m, 0, i] = x0, X_out[m, t+1, i] = model_m(X_out[m, t, i], V[t, i]): bit for bit what mppi_model_rollout returns on a lone
+ *     MPPI_MODEL_MLP handle holding member m's weights and this normalisation.
+ *   sse_out[m, j] = sum over t = 0..T and i of (X[m, t, i, j] - G[t, i, j])^2: fp32 per trajectory (t ascending) and per 16 trajectories
+ *     (a fixed pairwise tree), then the blocks of 16 in order in fp64. A member whose trajectories overflow reports a non-finite sse of its
+ *     own; the other members are unaffected. Deterministic.
+ * Only the weights are read: Adam moments, step counter, data and splits are untouched, and the next train returns the bits it would have
+ * returned. The call's device buffers are its own, grown on demand and freed by mppi_learner_wide_batch_destroy.
+ * Refused before the device is touched, the batch stays usable: MPPI_ERR_INVALID_ARG for model, x0 or V NULL, both outputs NULL, sse_out
+ * without G, n < 1, T < 1, n * T > 2^30, kx not 1 or n, an xstd entry equal to 0; MPPI_ERR_UNSUPPORTED for a model_kind other than
+ * MPPI_MODEL_MLP, for s_dim != 2 a_dim or a_dim outside 1..4, and for a batch whose widths are not [3 a_dim, 256, 256, 2 a_dim]. */
+mppi_status mppi_learner_wide_batch_validate(mppi_learner_wide_batch *wb, const mppi_learner_model *model,
+                                             const float *x0 /* [kx, s], kx in {1, n} */, int kx, const float *V /* [T, n, a] */,
+                                             const float *G /* [T+1, n, s] or NULL */, int n, int T,
+                                             double *sse_out /* [B, s] or NULL; needs G */, float *X_out /* [B, T+1, n, s] or NULL */);
 
 #ifdef __cplusplus
 }

@@ -188,6 +188,8 @@ SIGNATURES = {
 SIGNATURES.update({"mppi_learner_wide_batch_" + e: SIGNATURES["mppi_learner_batch_" + e] for e in (
     "create", "destroy", "last_error", "size", "set_data", "set_split", "set_weights", "get_weights", "reset_optimizer", "get_step", "train",
     "evaluate")})
+# ... and their trajectory validation: mppi_learner_batch_rollout's signature under a name of its own (WideLearnerBatch.validate)
+SIGNATURES["mppi_learner_wide_batch_validate"] = SIGNATURES["mppi_learner_batch_rollout"]
 
 _lib = None
 
@@ -1174,21 +1176,8 @@ class _LearnerBatchBase:
         return int(v.value)
 
 
-class WideLearnerBatch(_LearnerBatchBase):
-    """RAII wrapper of one mppi_learner_wide_batch: n_members learners of the [in, 256, 256, out] network (in, out <= 32) that share one
-    data pool and step in the same launches (mppi_learner_wide_batch.hip). LearnerBatch's methods and meaning, member for member
-    bit-identical to a lone wide Learner given the member's rows. It has no rollout: trajectory validation of wide members is not built."""
-    _PREFIX = "mppi_learner_wide_batch_"
-
-
-class LearnerBatch(_LearnerBatchBase):
-    """RAII wrapper of one mppi_learner_batch: n_members narrow learners (widths <= 32, 1-4 layers) that share one data pool and
-    step in the same launches (mppi_learner_batch.hip). Every member starts from `weights`, trains on its own rows of the pool
-    (set_split) with its own Adam rates, and is bit-identical to a lone Learner given those rows."""
-    _PREFIX = "mppi_learner_batch_"
-
-    # ---- trajectory validation (mppi_learner_batch_rollout, include/mppi_c.h)
-    _KINDS ={"mlp": MODEL_MLP, "nnauv": MODEL_NN_AUV, "nnauv_speed": MODEL_NN_AUV_SPEED}
+    # ---- trajectory validation (mppi_learner_batch_rollout / mppi_learner_wide_batch_validate, include/mppi_c.h): one body, two entry points
+    _KINDS = {"mlp": MODEL_MLP, "nnauv": MODEL_NN_AUV, "nnauv_speed": MODEL_NN_AUV_SPEED}
 
     @classmethod
     def model_desc(cls, model):
@@ -1204,11 +1193,8 @@ class LearnerBatch(_LearnerBatchBase):
         d["kind"] = cls._KINDS.get(d["kind"], d["kind"])
         return d
 
-    def rollout(self, model, x0, V, gt=None, trajectories=False):
-        """Every member's network rolled open-loop as the learned model `model` (model_desc) along the action sequences V [T, n, a] from
-        x0 [s] or [n, s], in ONE launch -> dict(sse [B, s] float64: the summed squared error against the ground truth gt [T+1, n, s], row 0
-        included (None without gt); X [B, T+1, n, s] float32 with trajectories=True: member m's is bit for bit
-        Handle(member m's weights).model_rollout(x0, V)). The batch itself does not change. Shapes are checked here: ValueError."""
+    def _roll(self, entry, who, model, x0, V, gt, trajectories):
+        """what LearnerBatch.rollout and WideLearnerBatch.validate do: the shape checks (ValueError), the call of `entry`, dict(sse[, X])"""
         d = self.model_desc(model)
         s, a = int(d["s_dim"]), int(d["a_dim"])
         V, x0 = np.asarray(V, dtype=np.float32), np.asarray(x0, dtype=np.float32)
@@ -1218,7 +1204,7 @@ class LearnerBatch(_LearnerBatchBase):
         if x0.shape not in [(s,), (1, s), (n, s)]:
             raise ValueError("x0 must have shape (%d,), (1, %d) or (%d, %d), not %s" % (s, s, n, s, x0.shape))
         if gt is None and not trajectories:
-            raise ValueError("rollout: nothing to return without gt and without trajectories")
+            raise ValueError("%s: nothing to return without gt and without trajectories" % who)
         x0, V = np.ascontiguousarray(x0).reshape(-1, s), np.ascontiguousarray(V)
         G = None
         if gt is not None:
@@ -1232,9 +1218,38 @@ class LearnerBatch(_LearnerBatchBase):
         desc = LearnerModel(int(d["kind"]), s, a, float(d.get("dt") or 0.0), *[fp(held[k]) for k in ("xmean", "xstd", "ymean", "ystd")])
         sse = np.zeros((self.B, s), np.float64) if G is not None else None
         X = np.zeros((self.B, T + 1, n, s), np.float32) if trajectories else None
-        self._check(self.lib.mppi_learner_batch_rollout(self.h, C.byref(desc), fp(x0), x0.shape[0], fp(V), fp(G), n, T,
-                                                        sse.ctypes.data_as(DP) if sse is not None else None, fp(X)))
+        self._check(entry(self.h, C.byref(desc), fp(x0), x0.shape[0], fp(V), fp(G), n, T, sse.ctypes.data_as(DP) if sse is not None else None, fp(X)))
         out = dict(sse=sse)
         if trajectories:
             out["X"] = X
         return out
+
+
+class WideLearnerBatch(_LearnerBatchBase):
+    """RAII wrapper of one mppi_learner_wide_batch: n_members learners of the [in, 256, 256, out] network (in, out <= 32) that share one
+    data pool and step in the same launches (mppi_learner_wide_batch.hip). LearnerBatch's methods and meaning, member for member
+    bit-identical to a lone wide Learner given the member's rows. LearnerBatch.rollout is `validate` here (mppi_learner_wide_batch_validate,
+    an entry point of its own): the members of a [3a, 256, 256, 2a] batch rolled open-loop in one launch (mppi_learner_wide_rollout.hip)."""
+    _PREFIX = "mppi_learner_wide_batch_"
+
+    def validate(self, model, x0, V, gt=None, trajectories=False):
+        """LearnerBatch.rollout for the wide members: every member's network rolled open-loop as the learned point-mass model `model`
+        (model_desc; MPPI_MODEL_MLP with s = 2a, a <= 4, the batch's widths [3a, 256, 256, 2a]) along the action sequences V [T, n, a] from
+        x0 [s] or [n, s], in ONE launch -> dict(sse [B, s] float64: the summed squared error against the ground truth gt [T+1, n, s], row 0
+        included (None without gt); X [B, T+1, n, s] float32 with trajectories=True: member m's is bit for bit
+        Handle(mlp=member m's weights).model_rollout(x0, V)). The batch itself does not change. Shapes are checked here: ValueError."""
+        return self._roll(self.lib.mppi_learner_wide_batch_validate, "validate", model, x0, V, gt, trajectories)
+
+
+class LearnerBatch(_LearnerBatchBase):
+    """RAII wrapper of one mppi_learner_batch: n_members narrow learners (widths <= 32, 1-4 layers) that share one data pool and
+    step in the same launches (mppi_learner_batch.hip). Every member starts from `weights`, trains on its own rows of the pool
+    (set_split) with its own Adam rates, and is bit-identical to a lone Learner given those rows."""
+    _PREFIX = "mppi_learner_batch_"
+
+    def rollout(self, model, x0, V, gt=None, trajectories=False):
+        """Every member's network rolled open-loop as the learned model `model` (model_desc) along the action sequences V [T, n, a] from
+        x0 [s] or [n, s], in ONE launch -> dict(sse [B, s] float64: the summed squared error against the ground truth gt [T+1, n, s], row 0
+        included (None without gt); X [B, T+1, n, s] float32 with trajectories=True: member m's is bit for bit
+        Handle(member m's weights).model_rollout(x0, V)). The batch itself does not change. Shapes are checked here: ValueError."""
+        return self._roll(self.lib.mppi_learner_batch_rollout, "rollout", model, x0, V, gt, trajectories)

@@ -34,7 +34,7 @@ UNITS = ([("mppi_launch_mlp.hip", ["MPPI_UNIT_A=%d" % a], "mlp_a%d" % a) for a i
          + [("mppi_launch_gen.hip", [], "gen"), ("mppi_launch_batch_gen.hip", [], "batch_gen"), ("mppi_launch_batch_nn.hip", [], "batch_nn"),
             ("mppi_learner.hip", [], "learner"), ("mppi_learner_wide.hip", [], "learner_wide"),
             ("mppi_learner_batch.hip", [], "learner_batch"), ("mppi_learner_rollout.hip", [], "learner_rollout"),
-            ("mppi_learner_wide_batch.hip", [], "learner_wide_batch"),
+            ("mppi_learner_wide_batch.hip", [], "learner_wide_batch"), ("mppi_learner_wide_rollout.hip", [], "learner_wide_rollout"),
             ("mppi_capi.hip", [], "capi"), ("mppi_capi_set.hip", [], "capi_set"), ("mppi_capi_step.hip", [], "capi_step"),
             ("mppi_capi_shard.hip", [], "capi_shard"), ("mppi_capi_log.hip", [], "capi_log"), ("mppi_capi_debug.hip", [], "capi_debug"),
             ("mppi_episode.hip", [], "episode"), ("mppi_episode_plant.hip", [], "episode_plant"),

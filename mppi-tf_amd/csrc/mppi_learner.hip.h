@@ -55,10 +55,25 @@ struct LbRollout {
     int kx, n, T, blocks;                 // blocks = ceil(n / kRollThreads)
 };
 
+// What k_wb_rollout takes, by value (mppi_learner_wide_rollout.hip; filled by mppi_learner_wide_batch_validate, which has checked every
+// field): the wide batch's weight block in its padded layout, the MPPI_MODEL_MLP normalisation and the trajectories. Device pointers.
+constexpr int kWideRollR = 16;    // trajectories of one member per workgroup (256 threads: one per hidden unit)
+constexpr int kWideRollMaxA = 4;  // a_dim 1..4, s_dim = 2 a_dim: the network is [3a, 256, 256, 2a]
+struct WbRollout {
+    const float *P;                       // [B][kWideParams]
+    int s, a;
+    float xmean[3 * kWideRollMaxA], xstd[3 * kWideRollMaxA], ymean[2 * kWideRollMaxA], ystd[2 * kWideRollMaxA];
+    const float *x0, *V, *G;              // [kx][s], [T][n][a], [T+1][n][s] or NULL
+    float *X, *part;                      // [B][T+1][n][s] or NULL; [B][blocks][s] (with G)
+    int kx, n, T, blocks;                 // blocks = ceil(n / kWideRollR)
+};
+
 } // namespace mppi_lrn
 
 // grid (blocks, B) on `st`; hipErrorInvalidValue for a (kind, s, a) no instance serves
 hipError_t mppi_lrn_launch_rollout(const mppi_lrn::LbRollout &r, int B, hipStream_t st);
+// grid (blocks, B) on `st`; hipErrorInvalidValue unless s = 2 a, a in 1..4
+hipError_t mppi_lrn_launch_wide_rollout(const mppi_lrn::WbRollout &r, int B, hipStream_t st);
 
 struct mppi_learner {
     int device = 0;

@@ -19,6 +19,8 @@
 // Adam just wrote, in the activation buffers the step is done with; its 64-row partials are summed in block order by the next step's
 // first launch (workgroup (0, 0) of the member) and, for the last step of a call, by one k_wb_mean.
 // Launches per Adam step: 9 (8 GEMMs + Adam), or 12 when test losses are asked for and some member has test rows. No float atomics.
+// Trajectory validation (mppi_learner_wide_batch_validate, at the end) reads P alone and rolls every member in ONE launch of k_wb_rollout,
+// which lives in mppi_learner_wide_rollout.hip: plain-order vector-ALU arithmetic, not the tiles above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -272,6 +274,8 @@ struct mppi_learner_wide_batch {
     float *A1 = nullptr, *A2 = nullptr, *D1 = nullptr, *D2 = nullptr, *D3 = nullptr; // [B][rows][256] x 4, [B][rows][32]; rows = max(cap, tcap)
     float *part = nullptr, *loss_part = nullptr, *test_part = nullptr;        // [B][chunks_max][kWideParams], [B][blocks_max], [B][tblocks_max]
     int cap = 0, tcap = 0, rows = 0, chunks_max = 0, blocks_max = 0, tblocks_max = 0, max_test = 0;
+    float *d_roll = nullptr; // mppi_learner_wide_batch_validate's inputs, partials and trajectories: one buffer, grown on demand
+    size_t roll_cap = 0;
     std::string err;
 };
 
@@ -388,6 +392,7 @@ extern "C" void mppi_learner_wide_batch_destroy(mppi_learner_wide_batch *wb)
     free_split_buffers(wb);
     wb_free(&wb->P); wb_free(&wb->M); wb_free(&wb->V); wb_free(&wb->step);
     wb_free(&wb->dX); wb_free(&wb->dY); wb_free(&wb->d_counts); wb_free(&wb->d_scale); wb_free(&wb->d_hp); wb_free(&wb->d_eval); wb_free(&wb->d_hist);
+    wb_free(&wb->d_roll);
     if (wb->stream) (void)hipStreamDestroy(wb->stream);
     delete wb;
 }
@@ -678,5 +683,77 @@ extern "C" mppi_status mppi_learner_wide_batch_evaluate(mppi_learner_wide_batch 
     if (loss_train) W_TRY(wb, hipMemcpy(loss_train, wb->d_eval, sizeof(float) * B, hipMemcpyDeviceToHost));
     if (test) W_TRY(wb, hipMemcpy(loss_test, wb->d_eval + B, sizeof(float) * B, hipMemcpyDeviceToHost));
     else if (loss_test) for (int m = 0; m < B; ++m) loss_test[m] = std::numeric_limits<float>::quiet_NaN();
+    return MPPI_OK;
+}
+
+// ---- trajectory validation: every member's network rolled open-loop in one launch (k_wb_rollout, mppi_learner_wide_rollout.hip).
+// mppi_learner_batch_rollout's refusals and buffer handling; it reads P only.
+extern "C" mppi_status mppi_learner_wide_batch_validate(mppi_learner_wide_batch *wb, const mppi_learner_model *model, const float *x0, int kx,
+                                                        const float *V, const float *G, int n, int T, double *sse_out, float *X_out)
+{
+    if (!wb) return MPPI_ERR_INVALID_ARG;
+    const std::string who = "mppi_learner_wide_batch_validate: ";
+    // every refusal before the device is touched
+    if (!model || !x0 || !V) return wfail(wb, MPPI_ERR_INVALID_ARG, who + "model, x0 [kx, s_dim] and V [T, n, a_dim] are required: NULL pointer");
+    if (!sse_out && !X_out) return wfail(wb, MPPI_ERR_INVALID_ARG, who + "sse_out and X_out are both NULL");
+    if (sse_out && !G) return wfail(wb, MPPI_ERR_INVALID_ARG, who + "sse_out needs the ground truth G [T+1, n, s_dim]");
+    if (n < 1 || T < 1) return wfail(wb, MPPI_ERR_INVALID_ARG, who + "n and T must be >= 1");
+    if ((size_t)n * (size_t)T > ((size_t)1 << 30)) return wfail(wb, MPPI_ERR_INVALID_ARG, who + "n * T must not exceed 2^30");
+    if (kx != 1 && kx != n) return wfail(wb, MPPI_ERR_INVALID_ARG, who + "x0 is [kx, s_dim] with kx in {1, n}");
+    if (model->model_kind != MPPI_MODEL_MLP)
+        return wfail(wb, MPPI_ERR_UNSUPPORTED, who + "model_kind must be MPPI_MODEL_MLP: the wide network is the point-mass controller's, no wide 13-state network exists");
+    if (model->a_dim < 1 || model->a_dim > kWideRollMaxA || model->s_dim != 2 * model->a_dim)
+        return wfail(wb, MPPI_ERR_UNSUPPORTED, who + "s_dim = " + std::to_string(model->s_dim) + ", a_dim = " + std::to_string(model->a_dim) +
+            ": MPPI_MODEL_MLP takes s_dim = 2 a_dim with a_dim in 1..4");
+    const int s_dim = model->s_dim, a_dim = model->a_dim, nin = s_dim + a_dim, B = wb->B;
+    if (wb->nin != nin || wb->nout != s_dim)
+        return wfail(wb, MPPI_ERR_UNSUPPORTED, who + "the batch's widths are [" + std::to_string(wb->nin) + ", 256, 256, " + std::to_string(wb->nout) +
+            "]: a_dim = " + std::to_string(a_dim) + " takes [" + std::to_string(nin) + ", 256, 256, " + std::to_string(s_dim) + "] (s_dim + a_dim -> s_dim)");
+    WbRollout r{};
+    for (int j = 0; j < 3 * kWideRollMaxA; ++j) { r.xmean[j] = 0.0f; r.xstd[j] = 1.0f; }
+    for (int j = 0; j < 2 * kWideRollMaxA; ++j) { r.ymean[j] = 0.0f; r.ystd[j] = 1.0f; }
+    for (int j = 0; j < nin; ++j) {
+        if (model->xmean) r.xmean[j] = model->xmean[j];
+        if (model->xstd) r.xstd[j] = model->xstd[j];
+        if (r.xstd[j] == 0.0f) return wfail(wb, MPPI_ERR_INVALID_ARG, who + "xstd[" + std::to_string(j) + "] is 0: the inputs are divided by it");
+    }
+    for (int j = 0; j < s_dim; ++j) {
+        if (model->ymean) r.ymean[j] = model->ymean[j];
+        if (model->ystd) r.ystd[j] = model->ystd[j];
+    }
+    const size_t s = (size_t)s_dim, a = (size_t)a_dim, rows = (size_t)n * (size_t)T, blocks = ((size_t)n + kWideRollR - 1) / kWideRollR;
+    r.P = wb->P; r.s = s_dim; r.a = a_dim; r.kx = kx; r.n = n; r.T = T; r.blocks = (int)blocks;
+    W_TRY(wb, hipSetDevice(wb->device));
+    // one buffer on the batch, carved into x0, V, G, the partials and X (each part a multiple of 64 floats: 256-byte starts)
+    const auto pad = [](size_t c) { return (c + 63) & ~(size_t)63; };
+    const size_t c_x = pad((size_t)kx * s), c_V = pad(rows * a), c_G = G ? pad((rows + n) * s) : 0, c_part = G ? pad((size_t)B * blocks * s) : 0,
+                 c_X = X_out ? pad((size_t)B * (rows + n) * s) : 0, total = c_x + c_V + c_G + c_part + c_X;
+    if (total > wb->roll_cap) {
+        W_TRY(wb, hipStreamSynchronize(wb->stream));
+        wb_free(&wb->d_roll); wb->roll_cap = 0;
+        if (mppi_status st = wb_alloc(wb, &wb->d_roll, total, "the trajectories [B][T+1][n][s_dim] and their inputs"); st != MPPI_OK) return st;
+        wb->roll_cap = total;
+    }
+    float *dx = wb->d_roll, *dV = dx + c_x, *dG = G ? dV + c_V : nullptr, *dpart = G ? dV + c_V + c_G : nullptr, *dX = X_out ? dV + c_V + c_G + c_part : nullptr;
+    hipStream_t q = wb->stream;
+    W_TRY(wb, hipMemcpyAsync(dx, x0, sizeof(float) * (size_t)kx * s, hipMemcpyHostToDevice, q));
+    W_TRY(wb, hipMemcpyAsync(dV, V, sizeof(float) * rows * a, hipMemcpyHostToDevice, q));
+    if (G) W_TRY(wb, hipMemcpyAsync(dG, G, sizeof(float) * (rows + n) * s, hipMemcpyHostToDevice, q));
+    r.x0 = dx; r.V = dV; r.G = dG; r.X = dX; r.part = dpart;
+    if (hipError_t e = mppi_lrn_launch_wide_rollout(r, B, q); e != hipSuccess) {
+        (void)hipStreamSynchronize(q);
+        return wfail(wb, MPPI_ERR_HIP, who + hipGetErrorString(e));
+    }
+    std::vector<float> part(sse_out ? (size_t)B * blocks * s : 0);
+    if (sse_out) W_TRY(wb, hipMemcpyAsync(part.data(), dpart, sizeof(float) * part.size(), hipMemcpyDeviceToHost, q));
+    if (X_out) W_TRY(wb, hipMemcpyAsync(X_out, dX, sizeof(float) * (size_t)B * (rows + n) * s, hipMemcpyDeviceToHost, q));
+    W_TRY(wb, hipStreamSynchronize(q));
+    if (sse_out) // the blocks of a member in block order, in fp64
+        for (int m = 0; m < B; ++m)
+            for (size_t j = 0; j < s; ++j) {
+                double acc = 0.0;
+                for (size_t b = 0; b < blocks; ++b) acc += (double)part[((size_t)m * blocks + b) * s + j];
+                sse_out[(size_t)m * s + j] = acc;
+            }
     return MPPI_OK;
 }

@@ -8,7 +8,8 @@ The reference's replay buffer is cpprb's ReplayBuffer (a ring of transitions): r
 k_fold_validation / grid_search (learner_base.py:83-216) train their k x R copies of the network as ONE LearnerBatch: every copy steps
 in the same launches (mppi_learner_batch.hip), and validate_fold rolls every copy along held-out trajectories in one more
 (mppi_learner_rollout.hip). A model whose network is [in, 256, 256, out] trains its copies as ONE WideLearnerBatch
-(mppi_learner_wide_batch.hip) instead; trajectory validation of wide members is not built, so val= / episode= are refused for it.
+(mppi_learner_wide_batch.hip) instead, rolled by WideLearnerBatch.validate (mppi_learner_wide_rollout.hip): k_fold_trajectory_validation
+serves both families; k_fold_validation / grid_search keep refusing val= / episode= for a wide model.
 TensorBoard logging and plotting are outside the path.
 """
 import os
@@ -159,11 +160,27 @@ class LearnerBase:
             self._check_val(val)
         if self.rb.n < 1:
             raise ValueError("k_fold_validation: the replay buffer holds no transitions")
+        if self._is_wide(self.model.get_weights()) and (val is not None or episode is not None):
+            raise ValueError("k_fold_validation: val= and episode= roll every member's network, and trajectory validation of wide members "
+                             "is not built into this method: use k_fold_trajectory_validation ([in, 256, 256, out] trains and tests as a "
+                             "WideLearnerBatch; choose by=\"test\")")
+        return self._k_fold(k, learningRate, epoch, val, writer, seed, episode)
+
+    def k_fold_trajectory_validation(self, k=10, learningRate=0.1, epoch=100, val=None, writer=None, seed=0):
+        """k_fold_validation(val=) for every model, narrow or wide: k x R copies trained as ONE LearnerBatch or ONE WideLearnerBatch, the
+        epochs in calls of 1, 10, 10, ... steps, and behind every epoch e with e % 10 == 0 every copy rolled along the held-out
+        trajectories val = (gtTrajs [kv, tau, s], actionSeqs [kv, tau, a]) in one launch (validate_fold: LearnerBatch.rollout or
+        WideLearnerBatch.validate) -> dict(train=[epoch, R, k], test=[epoch, R, k], val=[ceil(epoch / 10), R, k]), kept in self.kfold_log
+        and handed to `writer` as k_fold_validation does. On a narrow model the bits of k_fold_validation(val=)."""
+        self._check_val(val)
+        if self.rb.n < 1:
+            raise ValueError("k_fold_trajectory_validation: the replay buffer holds no transitions")
+        return self._k_fold(k, learningRate, epoch, val, writer, seed, None)
+
+    def _k_fold(self, k, learningRate, epoch, val, writer, seed, episode):
+        """the body of k_fold_validation and k_fold_trajectory_validation (their arguments, checked)"""
         w = self.model.get_weights()
         wide = self._is_wide(w)
-        if wide and (val is not None or episode is not None):
-            raise ValueError("k_fold_validation: val= and episode= roll every member's network, and trajectory validation of wide members "
-                             "is not built ([in, 256, 256, out] trains and tests as a WideLearnerBatch; choose by=\"test\")")
         rates = np.atleast_1d(np.asarray(learningRate, np.float32)).ravel()
         data = self.rb_trans()
         X, y = self.model.prepare_training_data(data["obs"], data["next_obs"], data["act"])
@@ -224,13 +241,13 @@ class LearnerBase:
     def validate_fold(self, batch, val, split=False, norm=False):
         """The multi-step error of every member of `batch` (learner_base.py:211-216 calls validate on each fold's model): each member's
         network, as this learner's model (its kind and normalisation), rolled tau - 1 steps from gtTrajs[:, 0] along actionSeqs, all
-        members in ONE launch (LearnerBatch.rollout) -> err [B] = sum of squared errors / (k tau s); the t = 0 term is zero and counts in
-        the mean, as in validate (learner_base.py:264-267). split: also errSplit [B, s]. norm: behind each, its twin in the network's
+        members in ONE launch (LearnerBatch.rollout; WideLearnerBatch.validate for a wide batch) -> err [B] = sum of squared errors /
+        (k tau s); the t = 0 term is zero and counts in the mean, as in validate (learner_base.py:264-267). split: also errSplit [B, s]. norm: behind each, its twin in the network's
         output units, sse / Ystd^2 (a model that normalises its last 6 outputs only, NNAUVModelSpeed: over those, as validate)."""
         gt, act = self._check_val(val)
         kv, tau, s = gt.shape
-        sse = batch.rollout(self.model, gt[:, 0], np.ascontiguousarray(np.swapaxes(act[:, :tau - 1], 0, 1)),
-                            gt=np.ascontiguousarray(np.swapaxes(gt, 0, 1)))["sse"]
+        roll = batch.rollout if hasattr(batch, "rollout") else batch.validate  # a LearnerBatch, or a WideLearnerBatch
+        sse = roll(self.model, gt[:, 0], np.ascontiguousarray(np.swapaxes(act[:, :tau - 1], 0, 1)), gt=np.ascontiguousarray(np.swapaxes(gt, 0, 1)))["sse"]
         errSplit = sse / float(kv * tau)
         out = [errSplit.mean(axis=1)]
         ystd = np.asarray(self.model.Ystd, np.float64).ravel()

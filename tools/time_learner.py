@@ -30,7 +30,12 @@ With --batch B[,B...] --validate it times the trajectory validation of a batch i
              Creating the B handles and pushing the members' weights into them is timed once, apart.
 The same clock, warm-up, alternation and medians; the figure is microseconds per validation of the whole set. Afterwards every member's
 trajectory is compared with its handle's: the bits must be equal.
-    tools/time_learner.py --batch 10,100 --validate [--ns 16,256] [--reps R] [--out FILE]"""
+    tools/time_learner.py --batch 10,100 --validate [--ns 16,256] [--reps R] [--out FILE]
+With --batch B[,B...] --wide --validate the same comparison is taken for the wide members (csrc/mppi_learner_wide_rollout.hip): the
+[9, 256, 256, 6] point-mass network, n = 16 trajectories (--ns) of T = 50 steps; (g) is one WideLearnerBatch.validate, (h) B lone
+MPPI_MODEL_MLP handles' model_rollout one after another (T launches each of a kernel that runs one thread per trajectory). One pass over
+the lone handles takes seconds, so a sample of `lone` is ONE pass where a sample of `batch` is ten calls.
+    tools/time_learner.py --batch 10,100 --wide --validate [--ns 16] [--reps R] [--out profiles/learner_wide_batch_validate_time.txt]"""
 import argparse
 import os
 import sys
@@ -154,47 +159,56 @@ def time_validate(o):
     import torch
     import mppi_tf_amd as m
     T, CALLS = 50, 10  # a sample of the clock is CALLS validations, each ending in its own synchronisation
-    head = ["tools/time_learner.py --batch --validate: %s, NNAUVModel [16,32,32,32,13], T = %d steps, reps %d of %d calls; medians of a host clock around calls that end" % (
-        torch.cuda.get_device_name(0), T, o.reps, CALLS),
-        "in a synchronisation; microseconds per validation of the whole set of B networks (min-max), alternating rounds; batch = one LearnerBatch.rollout",
-        "(1 launch, sse on the device), lone = B handles holding the members' weights, each model_rollout (T + 1 launches) + the sse on the host;",
+    LONE_CALLS = 1 if o.wide else CALLS  # one pass over B lone wide handles takes seconds
+    dims, s_dim, a_dim = (WIDE, 6, 3) if o.wide else (NARROW, 13, 6)
+    what = "NNPointMassModel [9,256,256,6]" if o.wide else "NNAUVModel [16,32,32,32,13]"
+    call = "WideLearnerBatch.validate" if o.wide else "LearnerBatch.rollout"
+    head = ["tools/time_learner.py --batch%s --validate: %s, %s, T = %d steps, reps %d of %d calls%s; medians of a host clock around calls that end" % (
+        " --wide" if o.wide else "", torch.cuda.get_device_name(0), what, T, o.reps, CALLS, " (lone: of %d)" % LONE_CALLS if LONE_CALLS != CALLS else ""),
+        "in a synchronisation; microseconds per validation of the whole set of B networks (min-max), alternating rounds; batch = one %s" % call,
+        "(1 launch, sse on the device), lone = B handles holding the members' weights, each model_rollout (%s launches) + the sse on the host;" % ("T" if o.wide else "T + 1"),
         "setup = creating those B handles with the members' weights, once, not part of `lone`"]
     print("\n".join(head), flush=True)
     lines = list(head)
-    norm = dict(xmean=np.zeros(16, F32), xstd=np.ones(16, F32), ymean=np.zeros(13, F32), ystd=np.ones(13, F32))
-    desc = dict(kind="nnauv", s_dim=13, a_dim=6, dt=0.1, **norm)
+    norm = dict(xmean=np.zeros(dims[0], F32), xstd=np.ones(dims[0], F32), ymean=np.zeros(dims[-1], F32), ystd=np.ones(dims[-1], F32))
+    desc = dict(kind="mlp" if o.wide else "nnauv", s_dim=s_dim, a_dim=a_dim, dt=0.1, **norm)
     for n in o.ns:
         rng = np.random.default_rng(n)
-        x0 = np.zeros((n, 13), F32)
-        x0[:, :3], x0[:, 6], x0[:, 7:] = rng.uniform(-1, 1, (n, 3)), 1.0, rng.uniform(-0.3, 0.3, (n, 6))
-        V = rng.standard_normal((T, n, 6)).astype(F32)
-        G = (np.broadcast_to(x0, (T + 1, n, 13)) + 0.05 * rng.standard_normal((T + 1, n, 13))).astype(F32)
+        x0 = np.zeros((n, s_dim), F32)
+        if o.wide:
+            x0[:] = rng.uniform(-1, 1, (n, s_dim))
+        else:
+            x0[:, :3], x0[:, 6], x0[:, 7:] = rng.uniform(-1, 1, (n, 3)), 1.0, rng.uniform(-0.3, 0.3, (n, 6))
+        V = rng.standard_normal((T, n, a_dim)).astype(F32)
+        G = (np.broadcast_to(x0, (T + 1, n, s_dim)) + 0.05 * rng.standard_normal((T + 1, n, s_dim))).astype(F32)
         for B in o.batch:
-            nets = [make_net(NARROW, seed) for seed in range(B)]
+            nets = [make_net(dims, seed) for seed in range(B)]
             for net in nets:
                 net["W"][-1] *= F32(0.1)
-            batch = m.LearnerBatch(nets[0], B)
+            batch = (m.WideLearnerBatch if o.wide else m.LearnerBatch)(nets[0], B)
             for i, net in enumerate(nets):
                 batch.set_weights(net, member=i)
+            roll = batch.validate if o.wide else batch.rollout
             t0 = time.perf_counter()
-            lone = [m.Handle(k=1, tau=1, s_dim=13, a_dim=6, dt=0.1, sigma=np.eye(6, dtype=F32), goal=np.zeros(13, F32), nnauv=dict(net, **norm)) for net in nets]
+            kw = dict(k=1, tau=1, s_dim=s_dim, a_dim=a_dim, dt=0.1, sigma=np.eye(a_dim, dtype=F32), goal=np.zeros(s_dim, F32))
+            lone = [m.Handle(**kw, **{"mlp" if o.wide else "nnauv": dict(net, **norm)}) for net in nets]
             setup = (time.perf_counter() - t0) * 1e6
             G64 = G.astype(np.float64)
 
             def lone_all():
                 return np.stack([((h.model_rollout(x0, V, costs=False)[0].astype(np.float64) - G64) ** 2).sum(axis=(0, 1)) for h in lone])
 
-            runs = (("batch", lambda: batch.rollout(desc, x0, V, gt=G)["sse"]), ("lone", lone_all))
-            got = {k: f() for k, f in runs}  # warm-up of every shape
-            t = {k: [] for k, _ in runs}
+            runs = (("batch", lambda: roll(desc, x0, V, gt=G)["sse"], CALLS), ("lone", lone_all, LONE_CALLS))
+            got = {k: f() for k, f, _ in runs}  # warm-up of every shape
+            t = {k: [] for k, _, _ in runs}
             for _ in range(o.reps):
-                for k, f in runs:
+                for k, f, calls in runs:
                     t0 = time.perf_counter()
-                    for _ in range(CALLS):
+                    for _ in range(calls):
                         f()
-                    t[k].append((time.perf_counter() - t0) / CALLS * 1e6)
+                    t[k].append((time.perf_counter() - t0) / calls * 1e6)
             med = {k: float(np.median(v)) for k, v in t.items()}
-            X = batch.rollout(desc, x0, V, trajectories=True)["X"]
+            X = roll(desc, x0, V, trajectories=True)["X"]
             same = all(np.array_equal(X[i], lone[i].model_rollout(x0, V, costs=False)[0]) for i in range(B))
             rel = float(np.max(np.abs(got["batch"] - got["lone"]) / got["lone"]))
             line = ("n=%-4d B=%-4d batch %9.1f us (%.1f-%.1f)   lone %10.1f us (%.1f-%.1f)  = %6.2fx batch   per network: batch %.1f us, lone %.1f us   setup of the "
@@ -217,7 +231,7 @@ def main():
     ap.add_argument("--batch", type=lambda v: [int(x) for x in v.split(",")], help="B[,B...]: time a LearnerBatch of B members against B lone learners")
     ap.add_argument("--ns", type=lambda v: [int(x) for x in v.split(",")], default=None, help="rows of the pool, with --batch (264,4096); trajectories, with --validate (16,256)")
     ap.add_argument("--wide", action="store_true", help="with --batch: the [9, 256, 256, 6] network, a WideLearnerBatch against B lone wide learners")
-    ap.add_argument("--validate", action="store_true", help="with --batch: time LearnerBatch.rollout against B lone handles' model_rollout")
+    ap.add_argument("--validate", action="store_true", help="with --batch: time LearnerBatch.rollout (--wide: WideLearnerBatch.validate) against B lone handles' model_rollout")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--out", help="also write the table to this file")
@@ -225,9 +239,9 @@ def main():
     o = ap.parse_args()
     if o.validate and not o.batch:
         ap.error("--validate goes with --batch")
-    if o.wide and (not o.batch or o.validate):
-        ap.error("--wide goes with --batch, not with --validate (trajectory validation of wide members is not built)")
-    o.ns = o.ns or ([16, 256] if o.validate else [264, 4096])
+    if o.wide and not o.batch:
+        ap.error("--wide goes with --batch")
+    o.ns = o.ns or (([16] if o.wide else [16, 256]) if o.validate else [264, 4096])
     if o.batch and not o.dry_run:
         return time_validate(o) if o.validate else time_batch(o)
     if o.dry_run:

@@ -254,10 +254,12 @@ def family_count(insts, group):
 
 
 # ---- the matrix --------------------------------------------------------------------------------------------------------------------------
-def spec(kind, hid, nh, a=6, dense=False, bx3=False, tuning=None, normalize=False, k=K, H=EDGE_H, member=0, batch=False):
-    """one case: a configuration + its shape, member number, Philox key and lambda multiplier"""
+def spec(kind, hid, nh, a=6, dense=False, bx3=False, tuning=None, normalize=False, k=K, H=EDGE_H, member=0, batch=False, start=None):
+    """one case: a configuration + its shape, member number, Philox key and lambda multiplier. start: None, or (name, state) — the start
+    state inputs() gives instead of its own (tests/attitude_util.py: a start attitude away from identity); the name enters the problem key
+    and the id. Without it nothing changes."""
     c = dict(kind=kind, a=a, hid=hid, nh=nh, dense=bool(dense), bx3=bool(bx3), tuning=dict(tuning or {}), normalize=bool(normalize), K=k, H=H,
-             member=member, batch=bool(batch), mult=MULT)
+             member=member, batch=bool(batch), mult=MULT, start=start)
     c["seed"] = 20000 + 1000 * a + 7 * H + 300 * member + (1 if dense else 0) + (50 if hid == 32 else 100 if hid == 16 else 0) + k % 97
     c["key"] = problem_key(c)
     tune = "".join("_%s%d" % (t.replace("mlp32_", "").replace("mlp_", "").replace("pc_", ""), v) for t, v in sorted(c["tuning"].items()))
@@ -268,8 +270,9 @@ def spec(kind, hid, nh, a=6, dense=False, bx3=False, tuning=None, normalize=Fals
 
 def problem_key(c):
     """what the oracle's problem (and hence lambda and the conditions) depends on: not the kernel the handle is tuned onto"""
-    return "%s_a%d_%dx%d_%s%s_K%d_H%d_m%d" % (c["kind"], c["a"], c["hid"], c["nh"], "dsig" if c["dense"] else "diag", "_norm" if c["normalize"] else "",
-                                              c["K"], c["H"], c["member"])
+    key = "%s_a%d_%dx%d_%s%s_K%d_H%d_m%d" % (c["kind"], c["a"], c["hid"], c["nh"], "dsig" if c["dense"] else "diag", "_norm" if c["normalize"] else "",
+                                             c["K"], c["H"], c["member"])
+    return key + ("_%s" % c["start"][0] if c.get("start") else "")
 
 
 def cfg_of(c, batch=None):
@@ -496,7 +499,10 @@ def inputs(c):
     """x and the nominal sequence as the learned tests make them: the point mass x = 0.2 randn, the 13-state models the tests' X0 with the
     position and the velocities moved; U = 0.1 randn"""
     rng = np.random.default_rng(c["seed"])
-    if c["kind"] == "pm":
+    if c.get("start"):
+        x = np.array(c["start"][1], np.float64)  # (the draws below keep their places in the stream)
+        rng.uniform(-0.5, 0.5, 3), rng.uniform(-0.1, 0.1, 6)
+    elif c["kind"] == "pm":
         x = 0.2 * rng.standard_normal(2 * c["a"])
     else:
         x = X13.copy()

@@ -2,7 +2,9 @@
 HEADER — min / max, a reciprocal, an odd polynomial in fused multiply-adds, two quadrant folds, the sign — against fp64 arctan2 over all four
 quadrants. The claim in the header's comment (within 2 ulp wherever |result| is not tiny) holds with a correctly rounded reciprocal; v_rcp_f32 is
 good to 1 ulp, which in the worst direction everywhere adds one more (3.1 ulp, 5e-7 rad absolute) — both bars are held here on the CPU;
-on the GPU the kernel that uses it is held to the fp64 oracle by tests/test_auv_gpu.py (costs 2e-5 relative, U' 1e-5)."""
+on the GPU the kernel that uses it is held to the fp64 oracle by tests/test_auv_gpu.py near the identity attitude (costs 2e-5 relative, U' 1e-5) and by
+tests/test_attitude_gpu.py — the GPU side of atan2_pose — in every octant of yaw and roll, with waves that straddle each fold, pitch to +-1.36 and
+across the +-pi cut."""
 import os
 import re
 

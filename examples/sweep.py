@@ -17,6 +17,9 @@ fp32 (one ulp apart), and the closed loop at these temperatures amplifies that t
 With --plant-mass m1,m2,... (and --on-device) the grid runs once per plant mass, all of them as ONE batch: member (point, mass) plans with
 the config's mass and its state is stepped by a separate plant handle of that mass (run_episode(..., plant=[...]), a plant per member);
 the table gains the plant-mass column and says which setting survives a vehicle that is not the modelled one.
+With --on-device the table also says whether each lambda WEIGHS the samples sensibly, from the step statistics the episode logs on the device
+(run_episode(..., stats=True)): ess/K, the effective sample size as a share of the samples, mean over the episode (near 1: the update is the
+plain mean of the noise; near 1/K: one sample holds all the weight), and needle, the share of steps with an effective sample size below 2.
 The reference sweeps its ellipse task; a batch refuses the 2D ellipse cost (ElipseCost), so this sweep runs the static task."""
 import argparse
 import itertools
@@ -81,17 +84,22 @@ def main():
     X = np.zeros((n, s), np.float32)
     t0 = time.perf_counter()
     plants = {pm: m.Handle(k=1, tau=1, s_dim=s, a_dim=a, dt=dt, mass=pm) for pm in masses if pm is not None}  # only their model is used
+    ess_cols = None
     if o.on_device:
-        X = hb.run_episode(X, o.steps, plant=[plants[pm] for pm in plant_of] if plants else None)[0][-1]
+        Xs, _, _, st = hb.run_episode(X, o.steps, plant=[plants[pm] for pm in plant_of] if plants else None, stats=True)
+        X = Xs[-1]
+        ess_cols = (st.ess.mean(axis=0) / st.k, (st.ess < 2.0).mean(axis=0))  # per grid point, over the steps
     else:
         for _ in range(o.steps):
             X = plant(X, hb.next(X), dt, mass)
     wall = time.perf_counter() - t0
     dist = np.linalg.norm(X[:, 0::2] - goal[0::2], axis=1)
     mass_col = (lambda pm: " %10.3g" % pm) if plants else (lambda pm: "")
-    print("%8s %8s %8s %8s%s  %s" % ("lambda", "upsilon", "gamma", "noise", " plant mass" if plants else "", "final goal distance"))
-    for (lam, ups, gam, noise), pm, d in zip(grid, plant_of, dist):
-        print("%8.3g %8.3g %8.3g %8.3g%s  %.4f" % (lam, ups, gam, noise, mass_col(pm), d))
+    print("%8s %8s %8s %8s%s  %s%s" % ("lambda", "upsilon", "gamma", "noise", " plant mass" if plants else "", "final goal distance",
+                                      "    ess/K   needle" if ess_cols else ""))
+    for i, ((lam, ups, gam, noise), pm, d) in enumerate(zip(grid, plant_of, dist)):
+        print("%8.3g %8.3g %8.3g %8.3g%s  %.4f%s" % (lam, ups, gam, noise, mass_col(pm), d,
+                                                    "%22.4f %8.2f" % (ess_cols[0][i], ess_cols[1][i]) if ess_cols else ""))
     best = int(np.argmin(dist))
     print("%d grid points, %d steps in one batch: %.2f s (%.1f us per batched step); best: lambda %.3g upsilon %.3g gamma %.3g noise %.3g%s "
           "(%.4f)" % (n, o.steps, wall, wall / max(o.steps, 1) * 1e6, *grid[best], (" on plant mass %.3g" % plant_of[best]) if plants else "",

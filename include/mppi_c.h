@@ -563,6 +563,48 @@ mppi_status mppi_run_episode_plant(mppi_handle *h, mppi_handle *const *plants, i
 mppi_status mppi_batch_run_episode_plant(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x, int n_steps,
                                          const float *goals, const float *disturbance, float *X_out, float *U_out, float *C_out);
 
+/* ---- step statistics: what the observer logs per control step (observer_base.py:101-187), computed on the device -------------------------
+ * The MPPI_DBG_* items are the raw arrays of the last step; these are the per-step scalars and histograms a user tunes lambda by, read from
+ * the same buffers (the sample costs, beta, eta, the cost buffer and temperature MPPI_DBG_WEIGHTS weighs) by ONE launch, one workgroup per
+ * member, fp64 sums in a fixed order (no float atomics): the same inputs give the same bits. Per sample k, exactly MPPI_DBG_WEIGHTS'
+ * quantities: arg_k = t (c'_k - beta) in fp32 (t = -1/lambda, or the step's temperature under normalize_cost; c' the costs the weights were
+ * made from), e_k = expf(arg_k). A sample whose raw cost (MPPI_DBG_COSTS) is not finite is counted in N_NONFINITE and left out of every
+ * sum, maximum and histogram. stats[MPPI_N_STEP_STATS] per member: */
+#define MPPI_N_STEP_STATS 9
+#define MPPI_STEP_STAT_BINS 32
+enum { MPPI_STAT_BETA = 0,        /* MPPI_DBG_BETA, the bits unchanged                                                              */
+       MPPI_STAT_ETA = 1,         /* MPPI_DBG_ETA, the bits unchanged (the observer's nabla; Nabla_percent = ETA / K)               */
+       MPPI_STAT_ESS = 2,         /* effective sample size (sum e)^2 / sum e^2, from the launch's own sums: 1 .. K                  */
+       MPPI_STAT_ENTROPY = 3,     /* -sum w ln w of the weights w = e / sum e, as ln S1 - (sum e arg) / S1: 0 .. ln K               */
+       MPPI_STAT_COST_MEAN = 4,   /* mean of the finite raw costs                                                                   */
+       MPPI_STAT_COST_STD = 5,    /* their population standard deviation (second pass, about the mean)                              */
+       MPPI_STAT_COST_MAX = 6,    /* the largest finite raw cost                                                                    */
+       MPPI_STAT_BEST_INDEX = 7,  /* the lowest k whose raw cost is the smallest finite one (the observer's best_id); exact as a float */
+       MPPI_STAT_N_NONFINITE = 8  /* how many raw costs are not finite                                                              */ };
+/* hist_cost[32] (the observer's All_cost): linear bins over [cmin, COST_MAX] of the finite raw costs, bin = min(31, (int)((c - cmin) *
+ * (32.0f / (COST_MAX - cmin)))) in fp32, every sample in bin 0 when COST_MAX = cmin. hist_weight[32] (exponenetial_argument / Weights):
+ * octaves below the best sample, bin = min(31, (int)(-arg * 1.442695f)): bin j holds the samples whose weight lies in (2^-(j+1), 2^-j] of
+ * the best one's. Both sum to K_local - N_NONFINITE. Without a finite cost the five statistics of indices 2..6 are NaN and BEST_INDEX -1.
+ * Statistics of the LAST step of the handle (mppi_next*, mppi_batch_next*, an episode's last step); synchronous; host pointers, any of
+ * which may be NULL. They only observe: nothing a step reads is written. A pre-launched pipeline is drained and an armed launch retired
+ * first, as by any entry point (neither leaves a cost or beta of a step that did not complete).
+ * MPPI_ERR_INVALID_ARG: no step has run yet (or mppi_update has overwritten beta and eta since), mppi_batch_step_stats on a lone handle.
+ * MPPI_ERR_UNSUPPORTED: mppi_step_stats on a batched handle, a sharded handle (the costs of one rank are not the step's), 2^24 or more
+ * samples per member (BEST_INDEX would not be exact). Nothing is enqueued before a refusal. */
+mppi_status mppi_step_stats(mppi_handle *h, float *stats /* [9] */, uint32_t *hist_cost /* [32] */, uint32_t *hist_weight /* [32] */);
+mppi_status mppi_batch_step_stats(mppi_handle *h, float *stats /* [B, 9] */, uint32_t *hist_cost /* [B, 32] */, uint32_t *hist_weight /* [B, 32] */);
+/* mppi_run_episode / mppi_run_episode_plant (plants == NULL and n_plants == 0: the handle's own model) with the statistics of EVERY step
+ * logged: one more launch per step, enqueued right behind the control step; the rows travel in the episode's staging and are copied out
+ * with X, U and C — no host wait inside. X, U, C and where the handle ends are bit for bit the plain episode's. The batched entry has a
+ * member axis after the step axis. Every refusal of the plain episodes and of mppi_step_stats (but "no step has run yet") applies. */
+mppi_status mppi_run_episode_stats(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x, int n_steps,
+                                   const float *goals, const float *disturbance, float *X_out, float *U_out, float *C_out,
+                                   float *S_out /* [n_steps, 9] */, uint32_t *Hc_out /* [n_steps, 32] */, uint32_t *Hw_out /* [n_steps, 32] */);
+mppi_status mppi_batch_run_episode_stats(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x, int n_steps,
+                                         const float *goals, const float *disturbance, float *X_out, float *U_out, float *C_out,
+                                         float *S_out /* [n_steps, B, 9] */, uint32_t *Hc_out /* [n_steps, B, 32] */,
+                                         uint32_t *Hw_out /* [n_steps, B, 32] */);
+
 /* ---- open-loop rollouts: the handle's model rolled along n GIVEN action sequences, every state and its cost written out ------------------
  * "Where does this model go if I apply these actions?" in one call with no host wait inside: the nominal plan, the plan of a chosen sample
  * (V = U + eps[k]), or the H-step open-loop error of a learned model along recorded actions. The step axis comes first and the trajectory

@@ -15,12 +15,12 @@ hand-written HIP for gfx950 in csrc/, reached through the C-ABI of include/mppi_
 """
 from . import build as _build  # noqa: F401
 from ._lib import (ACTION_COST_CPP, ACTION_COST_PY, CSV_REFERENCE, CSV_ROUNDTRIP, DBG_AUX, DBG_BETA, DBG_COSTS, DBG_ETA, DBG_NOISE,
-                   DBG_U_UPDATED, DBG_WEIGHTS, BatchHandle, Handle, MppiError, load)
+                   DBG_U_UPDATED, DBG_WEIGHTS, BatchHandle, Handle, MppiError, StepStats, load)
 from .controller import ControllerBase, ControllerBaseCpp, CostBase, ElipseCost, NNPointMassModel, PointMassModel, StaticCost
 from .auv import AUVModel, ElipseCost3D, NNAUVModel, NNAUVModelSpeed, StaticQuatCost
 from .learner import LearnerBase, kfold_indices
 from ._lib import Learner, LearnerBatch, WideLearnerBatch
 
-__all__ = ["Handle", "BatchHandle", "MppiError", "load", "ControllerBase", "ControllerBaseCpp", "CostBase", "PointMassModel", "NNPointMassModel",
+__all__ = ["Handle", "BatchHandle", "StepStats", "MppiError", "load", "ControllerBase", "ControllerBaseCpp", "CostBase", "PointMassModel", "NNPointMassModel",
            "StaticCost", "ElipseCost", "AUVModel", "NNAUVModel", "NNAUVModelSpeed", "StaticQuatCost", "ElipseCost3D", "LearnerBase", "Learner", "LearnerBatch", "WideLearnerBatch", "kfold_indices", "ACTION_COST_CPP", "ACTION_COST_PY", "DBG_COSTS", "DBG_BETA", "DBG_ETA", "DBG_WEIGHTS",
            "DBG_NOISE", "DBG_U_UPDATED", "DBG_AUX", "CSV_REFERENCE", "CSV_ROUNDTRIP"]

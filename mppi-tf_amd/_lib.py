@@ -5,6 +5,7 @@ torch is imported before the library is loaded on purpose: torch's wheel bundles
 libamdhip64.so.7; loading it first makes our library bind to that same HIP runtime instance
 (same soname) instead of bringing a second runtime into the process.
 """
+import collections
 import ctypes as C
 import os
 
@@ -27,6 +28,8 @@ P2P_FAULTS = {"": 0, "export": 1, "probe": 2}
 
 FP = C.POINTER(C.c_float)
 DP = C.POINTER(C.c_double)
+UP = C.POINTER(C.c_uint32)
+N_STEP_STATS, STEP_STAT_BINS = 9, 32  # MPPI_N_STEP_STATS, MPPI_STEP_STAT_BINS
 
 
 class MppiError(RuntimeError):
@@ -150,6 +153,11 @@ SIGNATURES = {
     # ... against a separate plant: another handle's model (run_episode(..., plant=))
     "mppi_run_episode_plant": (C.c_int, [_H, C.POINTER(_H), C.c_int, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
     "mppi_batch_run_episode_plant": (C.c_int, [_H, C.POINTER(_H), C.c_int, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP]),
+    # step statistics (Handle.step_stats, BatchHandle.step_stats) and the episodes that log them per step (run_episode(..., stats=True))
+    "mppi_step_stats": (C.c_int, [_H, FP, UP, UP]),
+    "mppi_batch_step_stats": (C.c_int, [_H, FP, UP, UP]),
+    "mppi_run_episode_stats": (C.c_int, [_H, C.POINTER(_H), C.c_int, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP, FP, UP, UP]),
+    "mppi_batch_run_episode_stats": (C.c_int, [_H, C.POINTER(_H), C.c_int, FP, C.c_int, C.c_int, FP, FP, FP, FP, FP, FP, UP, UP]),
     # open-loop rollouts of the handle's model (Handle.model_rollout, model_rollout_device)
     "mppi_model_rollout": (C.c_int, [_H, FP, C.c_int, FP, C.c_int, C.c_int, FP, FP]),
     "mppi_model_rollout_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -309,6 +317,21 @@ def _fill_config(lib, keep, k, tau, s_dim, a_dim, dt=0.1, mass=1.0, lam=1.0, gam
     return cfg
 
 
+class StepStats(collections.namedtuple("StepStats", "beta eta ess entropy cost_mean cost_std cost_max best_index n_nonfinite hist_cost "
+                                                  "hist_weight k")):
+    """The statistics of control steps (include/mppi_c.h, MPPI_STAT_*): every field but k is an array over the leading axes of the call
+    ([] for a lone handle's last step, [n] for a batch's, a step axis in front for an episode); hist_cost and hist_weight have 32 bins as
+    their last axis; best_index and n_nonfinite are integers; k is the sample count per member, so ess / k is the observer's scale."""
+    __slots__ = ()
+
+    @classmethod
+    def from_rows(cls, S, Hc, Hw, k):
+        """S [..., 9] float32 rows as the library wrote them, Hc / Hw [..., 32] uint32"""
+        cols = [S[..., i] for i in range(N_STEP_STATS)]
+        cols[7], cols[8] = cols[7].astype(np.int64), cols[8].astype(np.int64)
+        return cls(*cols, Hc, Hw, int(k))
+
+
 class _HandleBase:
     """What a lone controller (Handle) and a batch (BatchHandle) share: one mppi_handle `h` of `lib`, owned until close()."""
 
@@ -376,10 +399,18 @@ class _HandleBase:
     def synchronize(self):
         self._check(self.lib.mppi_synchronize(self.h))
 
-    def _run_episode(self, name, lead, x0, n_steps, goals, disturbance, plant=None):
+    def _step_stats(self, name, lead):
+        """the statistics of the last step through the entry point `name`; lead as in _run_episode"""
+        S = np.zeros((*lead, N_STEP_STATS), np.float32)
+        Hc, Hw = np.zeros((*lead, STEP_STAT_BINS), np.uint32), np.zeros((*lead, STEP_STAT_BINS), np.uint32)
+        self._check(getattr(self.lib, name)(self.h, fp(S), Hc.ctypes.data_as(UP), Hw.ctypes.data_as(UP)))
+        return StepStats.from_rows(S, Hc, Hw, self.k_local)
+
+    def _run_episode(self, name, lead, x0, n_steps, goals, disturbance, plant=None, stats=False):
         """n_steps closed-loop steps through the entry point `name` (mppi_run_episode / mppi_batch_run_episode); lead = () for a lone handle, (n,) for a batch:
         x0 [*lead, s], goals / disturbance [n_steps, *lead, s] or None -> (X [n_steps+1, *lead, s], U [n_steps, *lead, a], C [n_steps, *lead]).
         plant: None (the handle's own model, through `name`), a Handle, or for a batch a sequence of n Handles (through `name`_plant).
+        stats: True -> (X, U, C, StepStats) through `name`_stats, the statistics of every step with a leading step axis.
         Shapes and the plant count are checked here, before the library is called: a bad one raises ValueError."""
         n_steps = int(n_steps)
         if n_steps < 1:
@@ -403,6 +434,13 @@ class _HandleBase:
         X = np.zeros((n_steps + 1, *lead, self.s), np.float32)
         U = np.zeros((n_steps, *lead, self.a), np.float32)
         Cs = np.zeros((n_steps, *lead), np.float32)
+        if stats:
+            S = np.zeros((n_steps, *lead, N_STEP_STATS), np.float32)
+            Hc, Hw = np.zeros((n_steps, *lead, STEP_STAT_BINS), np.uint32), np.zeros((n_steps, *lead, STEP_STAT_BINS), np.uint32)
+            ph = None if plants is None else (_H * len(plants))(*[p.h for p in plants])
+            self._check(getattr(self.lib, name + "_stats")(self.h, ph, len(plants or ()), fp(x0), x0.size, n_steps, fp(goals), fp(disturbance),
+                                                           fp(X), fp(U), fp(Cs), fp(S), Hc.ctypes.data_as(UP), Hw.ctypes.data_as(UP)))
+            return X, U, Cs, StepStats.from_rows(S, Hc, Hw, self.k_local)
         if plants is None:
             self._check(getattr(self.lib, name)(self.h, fp(x0), x0.size, n_steps, fp(goals), fp(disturbance), fp(X), fp(U), fp(Cs)))
             return X, U, Cs
@@ -521,14 +559,21 @@ class Handle(_HandleBase):
         self._check(self.lib.mppi_next_with_noise(self.h, fp(x), x.size, fp(eps), eps.size, fp(u), u.size))
         return u
 
-    def run_episode(self, x0, n_steps, goals=None, disturbance=None, *, plant=None):
+    def step_stats(self):
+        """mppi_step_stats: the StepStats of the last step (effective sample size, entropy, cost moments, best sample, histograms),
+        computed on the device from what the step left there; refused before the first step and on a sharded handle"""
+        return self._step_stats("mppi_step_stats", ())
+
+    def run_episode(self, x0, n_steps, goals=None, disturbance=None, *, plant=None, stats=False):
         """mppi_run_episode: n_steps control steps on the device with the handle's own model as the plant, no host round trip between them.
         x0 [s]; goals [n_steps, s]: the goal in force at step t; disturbance [n_steps, s]: w_t added to the plant's x'
         -> (X [n_steps+1, s] the realised trajectory, U [n_steps, a] the controls, C [n_steps] the state cost of x_t under step t's goal).
         The handle ends where the host loop set_goal, next, model_next leaves it.
         plant: another Handle (lone, unsharded, same device, s_dim and a_dim) whose model steps the state instead (mppi_run_episode_plant):
-        x' is plant.model_next(x, u); nothing else of the plant is read, and nothing of it is written."""
-        return self._run_episode("mppi_run_episode", (), x0, n_steps, goals, disturbance, plant)
+        x' is plant.model_next(x, u); nothing else of the plant is read, and nothing of it is written.
+        stats=True (mppi_run_episode_stats): -> (X, U, C, StepStats), every field of the StepStats with a leading [n_steps] axis: what
+        step_stats() would return after each step, logged on the device; X, U and C are bit for bit those of stats=False."""
+        return self._run_episode("mppi_run_episode", (), x0, n_steps, goals, disturbance, plant, stats)
 
     def save_next(self, x_next):
         x = f32(x_next).ravel()
@@ -905,12 +950,18 @@ class BatchHandle(_HandleBase):
         """x_ptr [n, s_dim] -> u_ptr [n, a_dim], device pointers; enqueue only (stream: Handle.next_device's convention)"""
         self._check(self.lib.mppi_batch_next_device(self.h, x_ptr, u_ptr, self._stream(stream)))
 
-    def run_episode(self, X0, n_steps, goals=None, disturbance=None, *, plant=None):
+    def step_stats(self):
+        """mppi_batch_step_stats: the StepStats of every member's last step, fields [n] (histograms [n, 32]); row m has the bits of the
+        lone handle m's step_stats()"""
+        return self._step_stats("mppi_batch_step_stats", (self.n,))
+
+    def run_episode(self, X0, n_steps, goals=None, disturbance=None, *, plant=None, stats=False):
         """mppi_batch_run_episode: Handle.run_episode for every member at once. X0 [n, s]; goals / disturbance [n_steps, n, s]
         -> (X [n_steps+1, n, s], U [n_steps, n, a], C [n_steps, n]); member m's slices are its lone handle's episode.
         plant: a Handle every member's state is stepped with, or a sequence of n Handles, member m's at [m] (mppi_batch_run_episode_plant;
-        a learned plant is shared: a sequence of n > 1 learned plants is refused)."""
-        return self._run_episode("mppi_batch_run_episode", (self.n,), X0, n_steps, goals, disturbance, plant)
+        a learned plant is shared: a sequence of n > 1 learned plants is refused).
+        stats=True (mppi_batch_run_episode_stats): -> (X, U, C, StepStats) with fields [n_steps, n]."""
+        return self._run_episode("mppi_batch_run_episode", (self.n,), X0, n_steps, goals, disturbance, plant, stats)
 
     def model_rollout(self, *args, **kwargs):
         """refused: the members of a batch share one model, so an open-loop rollout is a lone handle's business (Handle.model_rollout)"""

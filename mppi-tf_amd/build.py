@@ -38,7 +38,7 @@ UNITS = ([("mppi_launch_mlp.hip", ["MPPI_UNIT_A=%d" % a], "mlp_a%d" % a) for a i
             ("mppi_capi.hip", [], "capi"), ("mppi_capi_set.hip", [], "capi_set"), ("mppi_capi_step.hip", [], "capi_step"),
             ("mppi_capi_shard.hip", [], "capi_shard"), ("mppi_capi_log.hip", [], "capi_log"), ("mppi_capi_debug.hip", [], "capi_debug"),
             ("mppi_episode.hip", [], "episode"), ("mppi_episode_plant.hip", [], "episode_plant"),
-            ("mppi_model_rollout.hip", [], "model_rollout")])
+            ("mppi_model_rollout.hip", [], "model_rollout"), ("mppi_step_stats.hip", [], "step_stats")])
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mppi_device.hip.h", "mppi_ablate.hip.h", "mppi_kernels.hip.h", "mppi_mlp2.hip.h", "mppi_mlp_small.hip.h", "mppi_mlp32.hip.h",
            "mppi_handle.hip.h", "mppi_capi.hip.h", "mppi_step.hip.h", "mppi_gen.hip.h", "mppi_mfma32.hip.h", "mppi_bx3.hip.h", "mppi_mlp32b.hip.h", "mppi_rollout_pc.inc",

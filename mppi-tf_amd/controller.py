@@ -411,6 +411,10 @@ class ControllerBase:
     def next_with_noise(self, state, noises):
         return self._h.next_with_noise(np.asarray(state, np.float32).reshape(-1), np.asarray(noises, np.float32))
 
+    def step_stats(self):
+        """What the reference's observer logs per control step (observer_base.py:101-187), of the last next(): Handle.step_stats()"""
+        return self._h.step_stats()
+
     def save(self, x, u, xNext):
         self._h.save_next(np.asarray(xNext, np.float32).reshape(-1))
         if self._log:  # controller_base.py:158-160

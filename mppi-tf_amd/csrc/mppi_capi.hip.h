@@ -1,6 +1,6 @@
 // mppi_capi.hip.h — what the units of the C-ABI share (mppi_capi.hip: creation; mppi_capi_set.hip: setters and accessors;
 // mppi_capi_step.hip: the control step; mppi_capi_shard.hip: the K-shard entries; mppi_capi_log.hip: the transition log;
-// mppi_capi_debug.hip: debug and helper entries): the error and entry macros, the routing predicates, the profiling slot, what a finish
+// mppi_capi_debug.hip: debug and helper entries; mppi_step_stats.hip: the step statistics): the error and entry macros, the routing predicates, the profiling slot, what a finish
 // takes, and the host functions one unit calls in another. Everything else is static in its unit. A kernel is launched only by the
 // unit that defines or instantiates it; another unit calls a host function of the owner.
 #pragma once
@@ -140,6 +140,18 @@ struct Finish {
 // the common case: the handle's own d_part (every slot: those no tile owns hold neutral records) onto its own sequence
 inline Finish own_records(const mppi_handle *h) { return Finish{h->d_part, 1, h->nbp, h->nbp, nullptr, h->U_cur(), h->U_other()}; }
 
+// What the weights of member `member`'s last step were made from (a lone handle: member 0) — the one selection MPPI_DBG_WEIGHTS
+// (mppi_capi_debug.hip) and the step statistics (mppi_step_stats.hip) share: the costs that were weighed (a lone handle's two-pass
+// normalizeCost: the raw costs at the step's temperature = the normalised costs at lambda), beta | eta, the member's constants (lambda)
+// and where the temperature is when it is not lambda.
+struct WeightInputs { const DevConsts *consts; const float *cost_w, *beta_eta, *nil_dev; };
+inline WeightInputs weight_inputs(const mppi_handle *h, int member)
+{
+    const float *cost = h->d_cost + (size_t)h->K_local * member;
+    return {h->dC + member, (h->normalize && !h->norm_two_pass) ? (const float *)h->d_cost2 : cost, h->d_dbg + 8 * (size_t)member,
+            h->norm_two_pass ? (const float *)(h->d_mm + 2) : (const float *)nullptr};
+}
+
 //  pc_eligible's horizon bound depends on pc_np, and pc_np on THIS shard's tile count (or a per-handle tuning): with
 // 132 < H <= 160 and ragged shards straddling 512 tiles one rank would make raw-cost records at the range temperature and another
 // normalised-cost records at lambda. A sharded handle therefore takes the fast form only below the bound that holds for every pc_np: the
@@ -205,6 +217,11 @@ mppi_status plain_step(mppi_handle *h, hipStream_t st, int src, const float *x_d
 // member_stride 0: one network (h->dM) for every row; 1: row i through the network of member i (a learned batch as its own plant)
 void mlp_step_ref(mppi_handle *h, hipStream_t st, const float *x, int kx, const float *v, int k, float *scratch, float *out_next,
                   int member_stride = 0);
+// ---- ... and of mppi_step_stats.hip. step_stats_refusal: why the handle's last step has no statistics (NULL: it has; *st the status) —
+// a sharded handle, 2^24 or more samples per member. launch_step_stats: ONE launch of k_step_stats behind a step on `st`, a workgroup per
+// member: stats [B][9], hist_cost [B][32], hist_weight [B][32], device pointers, all three required.
+const char *step_stats_refusal(const mppi_handle *h, mppi_status *st);
+hipError_t launch_step_stats(mppi_handle *h, hipStream_t st, float *stats, uint32_t *hist_cost, uint32_t *hist_weight);
 
 } // namespace mppi_capi
 using namespace mppi_capi;

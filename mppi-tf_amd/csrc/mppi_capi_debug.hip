@@ -32,11 +32,9 @@ static mppi_status debug_get(mppi_handle *h, int member, int what, float *out, s
         need = K;
         if (n != need) return fail(h, MPPI_ERR_INVALID_ARG, "wrong output size");
         HIP_TRY(h, hipMalloc((void **)&tmp, sizeof(float) * K));
-        // (a lone handle's two-pass normalizeCost: the raw costs at the step's temperature = the normalised costs at lambda)
-        hipLaunchKernelGGL(k_weights, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, (const DevConsts *)(h->dC + member),
-                           (h->normalize && !h->norm_two_pass) ? (const float *)h->d_cost2 : cost, (int)K, dbg,
-                           (float *)nullptr, (float *)nullptr, tmp,
-                           h->norm_two_pass ? (const float *)(h->d_mm + 2) : (const float *)nullptr);
+        const WeightInputs w = weight_inputs(h, member);
+        hipLaunchKernelGGL(k_weights, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, w.consts, w.cost_w, (int)K, w.beta_eta,
+                           (float *)nullptr, (float *)nullptr, tmp, w.nil_dev);
         src = tmp;
         break;
     }
@@ -279,6 +277,7 @@ extern "C" mppi_status mppi_update(mppi_handle *h, const float *cost, const floa
         dc.p, h->d_part, nullptr));
     else HIP_TRY(h, launch_tile(h, h->dC, h->stream, SRC_HBM, MODE_COSTS_GIVEN, h->d_x, dU.p, h->d_eps, dc.p, h->d_part, nullptr));
     h->norm_two_pass = 0; // records made from the GIVEN costs at lambda
+    h->stats_step = false; // ... whose beta and eta the finish below leaves in d_dbg, beside the last step's costs in d_cost
     // record = (beta, eta, V); then U' on a scratch copy of U (apply shifts it, so read U_updated)
     unsigned long long step_before = 0;
     HIP_TRY(h, hipMemcpyAsync(&step_before, h->d_step, sizeof(step_before), hipMemcpyDeviceToHost, h->stream));

@@ -662,16 +662,25 @@ static mppi_status check_plants(mppi_handle *h, const std::string &who, mppi_han
     return MPPI_OK;
 }
 
+// ---- ... with the statistics of every step logged (mppi_run_episode_stats / mppi_batch_run_episode_stats): ONE launch of k_step_stats
+// (mppi_step_stats.hip) right behind each control step, in front of the episode tail, writing row t of three more blocks of the staging
+// (S [n][B][9] | Hc [n][B][32] | Hw [n][B][32]: 73 words per step and member), copied out with X, U and C. Outputs may be NULL.
+struct EpisodeStats { float *S; uint32_t *Hc, *Hw; };
+
 static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0, int n_x, int n_steps, const float *goals,
                                const float *disturbance,
                                float *X_out, float *U_out, float *C_out, mppi_handle *const *plants = nullptr, int n_plants = 0,
-                               bool with_plant = false)
+                               bool with_plant = false, const EpisodeStats *stats = nullptr)
 {
     const int B = members(h), s = h->s, a = h->a;
     const std::string who = std::string(name) + ": ";
     if (!x0 || n_x != B * s) return fail(h, MPPI_ERR_INVALID_ARG, who + (h->batch ? "x0 must hold n * s_dim floats"
         : "x0 must hold s_dim floats"));
     if (n_steps < 1 || n_steps > (1 << 24)) return fail(h, MPPI_ERR_INVALID_ARG, who + "n_steps must be in [1, 2^24]");
+    if (stats) {
+        mppi_status why = MPPI_OK;
+        if (const char *msg = step_stats_refusal(h, &why)) return fail(h, why, who + msg);
+    }
     if (h->shard_count != 1) return fail(h, MPPI_ERR_INVALID_ARG, "sharded handle: use mppi_shard_partial / mppi_shard_finish");
     if (!h->no_rollout.empty()) return fail(h, MPPI_ERR_UNSUPPORTED, h->no_rollout);
     if (h->batch && !batch_eligible(h)) return fail(h, MPPI_ERR_UNSUPPORTED, kBatchStepRefusal(h));
@@ -694,7 +703,11 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
     const size_t oX = 0, oU = oX + (n + 1) * xs, oC = oU + n * us, oG = oC + n * B, oW = oG + (goals ? n * xs : 0), oS = oW +
         (disturbance ? n * xs : 0);
     const size_t oP = (oS + kScratch + 1) & ~(size_t)1; // the plant table: B pointers, 8-byte aligned
-    if (mppi_status st = ensure_episode_staging(h, plant.table.empty() ? oS + kScratch : oP + 2 * (size_t)B); st != MPPI_OK) return st;
+    const size_t oT = plant.table.empty() ? oS + kScratch : oP + 2 * (size_t)B; // the statistics, behind everything the plain episode stages
+    const size_t nS = n * B * MPPI_N_STEP_STATS, nH = n * B * MPPI_STEP_STAT_BINS;
+    if (mppi_status st = ensure_episode_staging(h, oT + (stats ? nS + 2 * nH : 0)); st != MPPI_OK) return st;
+    float *dS = h->d_ep + oT;
+    uint32_t *dHc = reinterpret_cast<uint32_t *>(dS + nS), *dHw = dHc + nH;
     float *dX = h->d_ep + oX, *dU = h->d_ep + oU, *dC = h->d_ep + oC, *dG = goals ? h->d_ep + oG : nullptr, *dW = disturbance
         ? h->d_ep + oW : nullptr;
     float *scratch = h->d_ep + oS;
@@ -725,6 +738,10 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
             TraceRange step_range(h, "mppi:step");
             if (mppi_status s_ = plain_step(h, st, SRC_PHILOX, x_t, nullptr, u_t); s_ != MPPI_OK) return s_;
         }
+        if (stats) {
+            const size_t r = (size_t)t * B;
+            HIP_TRY(h, launch_step_stats(h, st, dS + r * MPPI_N_STEP_STATS, dHc + r * MPPI_STEP_STAT_BINS, dHw + r * MPPI_STEP_STAT_BINS));
+        }
         TraceRange plant_range(h, "mppi:plant");
         if (learned && mk == MPPI_MODEL_MLP) {
             mlp_step_ref(stepper, st, x_t, B, u_t, B, scratch, x_next, (stepper == h && h->nn_batch) ? 1 : 0);
@@ -739,6 +756,9 @@ static mppi_status run_episode(mppi_handle *h, const char *name, const float *x0
     if (X_out) HIP_TRY(h, hipMemcpyAsync(X_out, dX, sizeof(float) * (n + 1) * xs, hipMemcpyDeviceToHost, st));
     if (U_out) HIP_TRY(h, hipMemcpyAsync(U_out, dU, sizeof(float) * n * us, hipMemcpyDeviceToHost, st));
     if (C_out) HIP_TRY(h, hipMemcpyAsync(C_out, dC, sizeof(float) * n * B, hipMemcpyDeviceToHost, st));
+    if (stats && stats->S) HIP_TRY(h, hipMemcpyAsync(stats->S, dS, sizeof(float) * nS, hipMemcpyDeviceToHost, st));
+    if (stats && stats->Hc) HIP_TRY(h, hipMemcpyAsync(stats->Hc, dHc, sizeof(uint32_t) * nH, hipMemcpyDeviceToHost, st));
+    if (stats && stats->Hw) HIP_TRY(h, hipMemcpyAsync(stats->Hw, dHw, sizeof(uint32_t) * nH, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     if (goals) for (int i = 0; i < s; ++i) h->hc.goal[i] = goals[(n - 1) * xs + i]; // the host mirror (member 0's)
     return MPPI_OK;
@@ -776,4 +796,26 @@ extern "C" mppi_status mppi_batch_run_episode_plant(mppi_handle *h, mppi_handle 
 {
     MPPI_BATCH_ONLY(h);
     return run_episode(h, "mppi_batch_run_episode_plant", x0, n_x, n_steps, goals, disturbance, X_out, U_out, C_out, plants, n_plants, true);
+}
+
+extern "C" mppi_status mppi_run_episode_stats(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x, int n_steps,
+                                              const float *goals, const float *disturbance, float *X_out, float *U_out, float *C_out,
+                                              float *S_out, uint32_t *Hc_out, uint32_t *Hw_out)
+{
+    if (!h) return MPPI_ERR_INVALID_ARG;
+    if (h->batch) return fail(h, MPPI_ERR_UNSUPPORTED,
+        "mppi_run_episode_stats: a batched handle runs its episodes through mppi_batch_run_episode_stats");
+    const EpisodeStats stats{S_out, Hc_out, Hw_out};
+    return run_episode(h, "mppi_run_episode_stats", x0, n_x, n_steps, goals, disturbance, X_out, U_out, C_out, plants, n_plants,
+        plants != nullptr || n_plants != 0, &stats);
+}
+
+extern "C" mppi_status mppi_batch_run_episode_stats(mppi_handle *h, mppi_handle *const *plants, int n_plants, const float *x0, int n_x,
+                                                    int n_steps, const float *goals, const float *disturbance, float *X_out, float *U_out,
+                                                    float *C_out, float *S_out, uint32_t *Hc_out, uint32_t *Hw_out)
+{
+    MPPI_BATCH_ONLY(h);
+    const EpisodeStats stats{S_out, Hc_out, Hw_out};
+    return run_episode(h, "mppi_batch_run_episode_stats", x0, n_x, n_steps, goals, disturbance, X_out, U_out, C_out, plants, n_plants,
+        plants != nullptr || n_plants != 0, &stats);
 }

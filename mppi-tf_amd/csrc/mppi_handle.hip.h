@@ -63,7 +63,8 @@ struct mppi_handle {
     float *U_cur() const { return d_Ubuf[u_cur] + u_off; }
     float *U_other() const { return d_Ubuf[1 - u_cur]; }
     float *d_Uupd = nullptr; // U' of the last step (MPPI_DBG_U_UPDATED)
-    void U_advance() { u_cur = 1 - u_cur; u_off = a; d_Uupd = d_Ubuf[u_cur]; }
+    bool stats_step = false; // d_cost and d_dbg are those of ONE control step (mppi_step_stats): up with every step, down when mppi_update rewrites d_dbg
+    void U_advance() { u_cur = 1 - u_cur; u_off = a; d_Uupd = d_Ubuf[u_cur]; stats_step = true; }
     // options of the Python reference's update: clip_act limits [a_min | a_max] and the Savitzky-Golay filter
     float *d_clip = nullptr;
     int sg_window = 0;

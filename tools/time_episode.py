@@ -7,7 +7,11 @@ With --plant the episode of (b) steps the state with SEPARATE plant handles (run
 that the work is the same: `shared` one plant handle for every member, `members` a plant handle per member (a table of B distinct pointers).
 Each figure is a host clock around `steps` steps; the three alternate, `reps` times, and the median is printed in us per batched step.
 Grids: the default grid of examples/sweep.py (5 x 4 x 5 x 3 = 300 members, its config and task files) and B = 1 (its first point).
-    tools/time_episode.py [--steps N] [--reps R] [--samples K] [--only host|episode|floor] [--plant shared|members] [--dry-run]"""
+With --stats, instead: what logging the step statistics costs (run_episode(..., stats=True): one k_step_stats launch per step, ONE workgroup
+per member) — the episode with and without them, alternating, median per step — at BASELINE configs[1] (point mass a = 2, K = 4096, H = 64:
+the one-launch step), configs[2] (a = 3, K = 65536, H = 64: one workgroup reads 256 KB of costs twice) and a batch of 32 point-mass
+controllers (the sweep's first 32 grid points). profiles/episode_stats_time.txt keeps the output.
+    tools/time_episode.py [--steps N] [--reps R] [--samples K] [--only host|episode|floor] [--plant shared|members] [--stats] [--dry-run]"""
 import argparse
 import itertools
 import os
@@ -84,6 +88,35 @@ def time_grid(m, B, samples, steps, reps, only=None, plants=None):
     return med
 
 
+def stats_cases(samples):
+    """name -> (class name, keywords, x0 shape) of the three --stats cases"""
+    pm = lambda a, K: dict(k=K, tau=64, s_dim=2 * a, a_dim=a, dt=0.1, mass=1.0, lam=1.0, sigma=(0.25 * np.eye(a)).astype(np.float32),
+                           goal=[1.0, 0.0, 0.5, 0.0, 0.75, 0.0][:2 * a], seed=1)
+    kw32 = sweep_kw(samples, 32)[0]
+    return {"configs[1] K=4096 H=64 a=2": ("Handle", pm(2, 4096), (4,)), "configs[2] K=65536 H=64 a=3": ("Handle", pm(3, 65536), (6,)),
+            "batch B=32 K=%d H=%d a=%d" % (kw32["k"], kw32["tau"], kw32["a_dim"]): ("BatchHandle", kw32, (32, kw32["s_dim"]))}
+
+
+def time_stats(m, samples, steps, reps):
+    for name, (cls, kw, shape) in stats_cases(samples).items():
+        hs = {False: getattr(m, cls)(**kw), True: getattr(m, cls)(**kw)}  # a handle each: the two never share a sequence
+        x0 = np.zeros(shape, np.float32)
+        for stats, h in hs.items():  # warm-up: code objects loaded, the staging allocated, clocks up
+            h.run_episode(x0, max(10, steps // 4), stats=stats)
+            h.run_episode(x0, steps, stats=stats)
+        t = {False: [], True: []}
+        for _ in range(reps):
+            for stats, h in hs.items():
+                t0 = time.perf_counter()
+                h.run_episode(x0, steps, stats=stats)
+                t[stats].append((time.perf_counter() - t0) / steps)
+        plain, logged = (float(np.median(t[k])) * 1e6 for k in (False, True))
+        print("%-30s episode %8.2f us per step, with statistics %8.2f us (%.2f-%.2f over %d reps): +%.2f us per step = %.0f %% of the step"
+              % (name, plain, logged, min(t[True]) * 1e6, max(t[True]) * 1e6, reps, logged - plain, 100.0 * (logged - plain) / plain), flush=True)
+        for h in hs.values():
+            h.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=300, help="steps per timed loop (the sweep's default: 300)")
@@ -92,10 +125,13 @@ def main():
     ap.add_argument("--only", choices=("host", "episode", "floor"), help="time one of the three alone")
     ap.add_argument("--plant", choices=("shared", "members"), help="the episode steps the state with separate plant handles, twins of the "
                                                                    "controller's model: one for all members, or one per member")
+    ap.add_argument("--stats", action="store_true", help="time the episode with and without the step statistics instead (three cases)")
     ap.add_argument("--dry-run", action="store_true", help="print the grids and build their keywords, time nothing (no GPU)")
     o = ap.parse_args()
     grids = (300, 1)
     if o.dry_run:
+        for name, (cls, kw, shape) in (stats_cases(o.samples).items() if o.stats else ()):
+            print("--stats %-30s %s x0 %s %s" % (name, cls, shape, sorted(kw)), flush=True)
         for B in grids:
             kw, dt, mass = sweep_kw(o.samples, B)
             print("B=%-3d K=%-5d H=%-3d a=%d  dt %g mass %g  %s" % (kw["n"], kw["k"], kw["tau"], kw["a_dim"], dt, mass, sorted(kw)), flush=True)
@@ -103,6 +139,8 @@ def main():
     import torch
     import mppi_tf_amd as m
     print("tools/time_episode.py: %s, steps %d, reps %d" % (torch.cuda.get_device_name(0), o.steps, o.reps), flush=True)
+    if o.stats:
+        return time_stats(m, o.samples, o.steps, o.reps)
     for B in grids:
         time_grid(m, B, o.samples, o.steps, o.reps, o.only, o.plant)
 

@@ -390,6 +390,8 @@ enum { MPPI_TUNE_FORCE_TILE_KERNEL = 0, /* 1: the LDS-tile rollout kernel instea
                                          * While armed the launch occupies the GPU; a launch whose x does not come in time aborts by itself and changes nothing.
                                          * Controls are bit-identical to the unarmed path. MPPI_ERR_UNSUPPORTED without a large-BAR device. */
        MPPI_TUNE_ARMED_ALWAYS = 12,     /* 1: arm behind every mppi_next whatever the gap between the last two calls (tests of the deadline path) */
+       MPPI_TUNE_FINISH_GENERIC = 14,   /* 1: the finish of a step on k_finish_cols (runtime record strides, every optional input decided in the kernel) instead of
+                                         * k_finish_cols_cm, the column-major fast path; a batched handle: k_finish_cols_batch as it was. Same results bit for bit (A/B timing) */
        MPPI_TUNE_PRELAUNCH = 13 };      /* default 0. 1: mppi_next_device on the handle's OWN stream (stream = NULL) runs PRE-LAUNCHED: steps alternate
                                          * between two streams of the handle, the rollout of step n+1 is resident and draws its noise while step n finishes, and takes
                                          * U' of step n from the finish kernel (<= 128 tiles: from the column waves of step n's one launch) as {value, tag} granules. x_dev must be complete when the call is made and stay

@@ -115,6 +115,17 @@ static hipError_t launch_rollout(mppi_handle *h, hipStream_t st, Route route, mp
     return e;
 }
 
+// Which instance of k_finish_cols_cm finishes these records, or -1: k_finish_cols. The fast path takes column-major records that fit a
+// thread's four slots (the tile records of a step; the folded records above 1024 tiles and the gathered shard records are row-major)
+// with at most one of the optional inputs: the verdict of an armed launch, the granules of a pre-launched one, a temperature on the device.
+static int finish_cm_mode(const mppi_handle *h, const Finish &f)
+{
+    if (h->finish_generic || f.sb != 1 || f.n < 1 || f.n > 4 * kThreads || h->a < 1) return -1;
+    const bool armed = f.armed_seq != 0, pre = f.pre.in != nullptr, norm = f.nil_dev != nullptr;
+    if ((int)armed + (int)pre + (int)norm > 1 || (pre && f.pre.out == nullptr) || (f.pre.out != nullptr && !pre)) return -1;
+    return armed ? FIN_ARMED : pre ? FIN_PRE : norm ? FIN_NORM : FIN_PLAIN;
+}
+
 // More than 1024 records are first folded 16:1 (k_combine_group) into row-major scratch.
 hipError_t launch_finish(mppi_handle *h, hipStream_t st, Finish f)
 {
@@ -142,7 +153,15 @@ hipError_t launch_finish(mppi_handle *h, hipStream_t st, Finish f)
                               h->hc.neg_inv_lambda, f.U_in, f.U_out, f.u_out, h->d_step, h->d_dbg, h->xchg_peers, h->shard_count,
                               h->shard_rank, ++h->xchg_seq,
                               h->xchg_timeout_ticks, h->d_xchg_status, h->d_xchg_dead, (const float *)h->d_clip);
-    else
+    else if (const int mode = finish_cm_mode(h, f); mode >= 0) {
+        // column-major records, one optional input at most: the instance of that protocol (k_finish_cols_cm)
+        const auto kern = mode == FIN_ARMED ? k_finish_cols_cm<FIN_ARMED> : mode == FIN_PRE ? k_finish_cols_cm<FIN_PRE>
+                        : mode == FIN_NORM ? k_finish_cols_cm<FIN_NORM> : k_finish_cols_cm<FIN_PLAIN>;
+        hipExtLaunchKernelGGL(kern, dim3(h->HA), dim3(kThreads), 0, st, kev.begin, kev.end, 0, f.recs, f.sc, f.n, h->HA, h->a,
+                              (1ull << 32) / (unsigned long long)h->a + 1ull, h->hc.neg_inv_lambda, f.U_in, f.U_out, f.u_out,
+                              f.record_out, f.apply, h->d_step, h->d_dbg, (const float *)h->d_clip, f.nil_dev,
+                              (const unsigned long long *)h->d_decision, f.armed_seq, f.pre);
+    } else
         hipExtLaunchKernelGGL(k_finish_cols, dim3(h->HA), dim3(kThreads), 0, st, kev.begin, kev.end, 0, f.recs,
                               f.sb, f.sc, f.n, h->HA, h->a,
                               h->hc.neg_inv_lambda, f.U_in, f.U_out, f.u_out, f.record_out, f.apply, h->d_step, h->d_dbg,

@@ -414,6 +414,104 @@ __device__ __forceinline__ void column_combine(Load ld, int nb, float neg_inv_la
     beta_out = beta; eta_out = eta; V_out = V;
 }
 
+// ---- the column-major fast path (r06) ---------------------------------------------------------------------------------------
+// The finish is a lone wave's chain between two dispatches: what it costs is the round trips and the instructions on that chain, not
+// bandwidth. column_combine_cm is column_combine for records stored column-major (element (b, j) at col_j[b]: the tile records of every
+// rollout kernel) with the chain cut down: the column bases stay in scalar registers, a thread's slots tid + 256 i are one vector
+// address with immediate offsets where the blocks are full, nothing between the entry and the twelve loads depends on memory, and the
+// two double ladders and the four expf run interleaved (no branch per slot: the loads are clamped, so a slot beyond nb is computed and
+// dropped by a select). The association IS column_combine's — thread t takes slots t, t + 256, t + 512, t + 768 in that order in
+// double, wave_sum_d's ladder, the four wave totals in order — and so are the bits (tests/test_finish_fast_path_gpu.py).
+// TAIL: nb may exceed 4 * 256 (a batched handle's members); a lone handle's launcher never passes more (launch_finish folds first).
+struct ColRecs { float bb[4], ee[4], vv[4]; };
+
+// The twelve loads, unconditional on clamped indices (see k_combine_group): scalar column base + one 32-bit vector offset per block.
+// (An unclamped arm for full blocks — tid * 4 alone and immediate offsets — does not survive hipcc: it merges the two arms' loads
+// behind the branch again and selects the addresses with moves. The clamp costs an add and a min per block.)
+__device__ __forceinline__ void col_loads(const float *__restrict__ cb, const float *__restrict__ ce, const float *__restrict__ cv,
+                                          int nb, ColRecs &r)
+{
+    const unsigned tid4 = threadIdx.x * 4u, last4 = (unsigned)(nb - 1) * 4u; // byte offsets: one shift for the four blocks
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned off = min(tid4 + (unsigned)(i * kThreads * 4), last4);
+        r.bb[i] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(cb) + off);
+        r.ee[i] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(ce) + off);
+        r.vv[i] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(cv) + off);
+    }
+}
+
+// A load that is requested where it is written. hipcc moves a plain load into the block of its first use: what thread 0 needs at the
+// very end would be fetched behind both barriers, a memory round trip on the lone thread's chain. A relaxed atomic load stays in
+// place and is only waited for at its use.
+template <class T>
+__device__ __forceinline__ T load_here(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// more(): the caller's own loads, requested right behind the records'; neg_inv_lambda is read after it (it may come from one of them)
+template <bool TAIL, class More>
+__device__ __forceinline__ void column_combine_cm(const float *__restrict__ cb, const float *__restrict__ ce, const float *__restrict__ cv,
+                                                  int nb, const float &neg_inv_lambda, More more, float *red_f, double (*red_d)[kThreads / 64],
+                                                  float &beta_out, double &eta_out, double &V_out)
+{
+    const int tid = threadIdx.x;
+    constexpr int PER = 4;
+    ColRecs q;
+    MPPI_FINISH_STOP(0, 0.f); // (timing-study builds only: mppi_ablate.hip.h)
+    col_loads(cb, ce, cv, nb, q);
+    more();
+    MPPI_FINISH_STOP(1, ((q.bb[0] + q.ee[0] + q.vv[0]) + (q.bb[1] + q.ee[1] + q.vv[1])) + ((q.bb[2] + q.ee[2] + q.vv[2]) + (q.bb[3] + q.ee[3] + q.vv[3])));
+    float bmin = INFINITY;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) bmin = fminf(bmin, (tid + i * kThreads < nb) ? q.bb[i] : INFINITY);
+    if constexpr (TAIL)
+        for (int b = tid + PER * kThreads; b < nb; b += kThreads) bmin = fminf(bmin, cb[b]);
+    bmin = wave_min(bmin);
+    if ((tid & 63) == 0) red_f[tid >> 6] = bmin;
+    __syncthreads();
+    float beta = red_f[0];
+#pragma unroll
+    for (int w = 1; w < kThreads / 64; ++w) beta = fminf(beta, red_f[w]);
+    MPPI_FINISH_STOP(2, beta + q.ee[0] + q.vv[0]);
+
+    float r[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) r[i] = expf(neg_inv_lambda * (q.bb[i] - beta)); // four independent chains
+    double se = 0.0, sv = 0.0;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const bool in = tid + i * kThreads < nb;
+        const double se_i = se + (double)r[i] * (double)q.ee[i], sv_i = sv + (double)r[i] * (double)q.vv[i];
+        se = in ? se_i : se;
+        sv = in ? sv_i : sv;
+    }
+    if constexpr (TAIL)
+        for (int b = tid + PER * kThreads; b < nb; b += kThreads) {
+            const float rb = expf(neg_inv_lambda * (cb[b] - beta));
+            se += (double)rb * (double)ce[b];
+            sv += (double)rb * (double)cv[b];
+        }
+    // wave_sum_d(se) and wave_sum_d(sv), level by level side by side
+    se = se + dpp_mov_d<0xB1>(se);  sv = sv + dpp_mov_d<0xB1>(sv);
+    se = se + dpp_mov_d<0x4E>(se);  sv = sv + dpp_mov_d<0x4E>(sv);
+    se = se + dpp_mov_d<0x141>(se); sv = sv + dpp_mov_d<0x141>(sv);
+    se = se + dpp_mov_d<0x140>(se); sv = sv + dpp_mov_d<0x140>(sv);
+    se = (readlane_d(se, 0) + readlane_d(se, 16)) + (readlane_d(se, 32) + readlane_d(se, 48));
+    sv = (readlane_d(sv, 0) + readlane_d(sv, 16)) + (readlane_d(sv, 32) + readlane_d(sv, 48));
+    if ((tid & 63) == 0) { red_d[0][tid >> 6] = se; red_d[1][tid >> 6] = sv; }
+    __syncthreads();
+    double eta = red_d[0][0], V = red_d[1][0];
+#pragma unroll
+    for (int w = 1; w < kThreads / 64; ++w) { eta += red_d[0][w]; V += red_d[1][w]; }
+    beta_out = beta; eta_out = eta; V_out = V;
+}
+
+// c mod a without a division in front of the loads: a_recip = 2^32 / a + 1 (finish_recip, computed once by the host), exact for
+// c < 2^32 / a (c < tau * a_dim here)
+__device__ __forceinline__ int finish_mod(int c, int a, unsigned long long a_recip)
+{
+    return c - (int)(((unsigned long long)(unsigned)c * a_recip) >> 32) * a;
+}
+
 // Behind a PRE-LAUNCHED rollout (k_step_pc<.., STEP_PRE>, mppi_step.hip.h): the sequence travels between the steps as 8-byte {value, tag}
 // granules — the finish of step n reads U from granules `in` (complete: its rollout waited for every one of them), writes the SHIFTED U' as
 // granules `out` tagged `tag` (what step n+1's rollout, already resident on the other stream, is polling for) beside the plain U_out, and
@@ -468,6 +566,68 @@ __global__ __launch_bounds__(kThreads) void k_finish_cols(
         }
     }
 }
+
+// k_finish_cols_cm: k_finish_cols for column-major records (sb == 1, nb <= 1024: what every plain, armed and pre-launched step passes),
+// same results bit for bit (MPPI_TUNE_FINISH_GENERIC puts a handle back on k_finish_cols). One instance per protocol, so that no
+// optional pointer decides anything in front of the loads: the kernel arguments arrive as one batch, then every global load the
+// kernel will need is in flight before the first wait — the twelve record loads, U[c] (or its granule), the step counter, the
+// limits, the temperature and the verdict. The verdict of an armed launch gates the stores only (an aborted launch still changes
+// nothing); u_old, lo, hi and step_old are consumed by thread 0 behind the second barrier. Limits off: the two loads read the
+// records instead and the selects drop them.
+enum { FIN_PLAIN = 0, FIN_ARMED = 1, FIN_PRE = 2, FIN_NORM = 3 };
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void k_finish_cols_cm(
+    const float *__restrict__ recs, int sc, int nb, int HA, int a, unsigned long long a_recip, float neg_inv_lambda,
+    const float *__restrict__ U_in, float *__restrict__ U_out, float *__restrict__ u_out,
+    float *__restrict__ record_out, int apply, unsigned long long *__restrict__ step_ctr, float *__restrict__ dbg,
+    const float *__restrict__ clip, const float *__restrict__ nil_dev, const unsigned long long *__restrict__ verdict, unsigned seq,
+    const FinishPre pre)
+{
+    __shared__ float red_f[kThreads / 64];
+    __shared__ double red_d[2][kThreads / 64];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    if constexpr (MODE == FIN_PRE) __builtin_amdgcn_s_setprio(3); // (the next step's rollout is resident around these waves, drawing noise — and waiting for them)
+    // what only thread 0's tail uses is requested with the rest of the arguments (hipcc otherwise fetches each where it is first used:
+    // three more waits on the lone thread's chain)
+    asm volatile("" ::"s"(U_out), "s"(u_out), "s"(record_out), "s"(apply), "s"(dbg), "s"(HA), "s"(neg_inv_lambda), "s"(seq));
+    if constexpr (MODE == FIN_PRE) asm volatile("" ::"s"(pre.out), "s"(pre.tag), "s"(pre.step));
+    float lo_ld = 0.0f, hi_ld = 0.0f, u_old = 0.0f;
+    unsigned long long step_old = pre.step, verdict_ld = 0ull;
+    const auto more = [&]() {
+        const int cj = finish_mod(c, a, a_recip);
+        const float *lim = clip != nullptr ? clip : recs; // (recs: any 2 a readable floats)
+        if constexpr (MODE == FIN_PRE) u_old = __uint_as_float((unsigned)load_here(pre.in + c));
+        else { u_old = load_here(U_in + c); step_old = load_here(step_ctr); }
+        if constexpr (MODE == FIN_NORM) neg_inv_lambda = load_here(nil_dev); // two-pass normalizeCost: the temperature of this step (k_cost_minmax)
+        if constexpr (MODE == FIN_ARMED) verdict_ld = load_here(verdict);
+        lo_ld = load_here(lim + cj);
+        hi_ld = load_here(lim + a + cj);
+    };
+    float beta;
+    double eta, V;
+    column_combine_cm<false>(recs, recs + sc, recs + (size_t)(2 + c) * sc, nb, neg_inv_lambda, more, red_f, red_d, beta, eta, V);
+    // behind an ARMED rollout launch (mppi_step.hip.h): the update applies only if tile 0 accepted launch `seq` (its verdict word {1, seq})
+    const bool go = MODE != FIN_ARMED || verdict_ld == (((unsigned long long)seq << 32) | 1ull);
+    if (tid == 0 && go) {
+        const float lo = clip != nullptr ? lo_ld : -INFINITY, hi = clip != nullptr ? hi_ld : INFINITY; // clip_act: [a_min | a_max], NULL = off
+        if (record_out != nullptr) {
+            record_out[2 + c] = (float)V;
+            if (c == 0) { record_out[0] = beta; record_out[1] = (float)eta; }
+        }
+        if (c == 0 && dbg != nullptr) { dbg[0] = beta; dbg[1] = (float)eta; }
+        if (apply) {
+            const float un = fminf(fmaxf(u_old + (float)(V / eta), lo), hi);
+            U_out[c] = un;            // U' ; the next step reads U_out + a (the shifted sequence)
+            if (c < a) u_out[c] = un; // mGetNew
+            if (c == 0) step_ctr[0] = step_old + 1ull;
+            if constexpr (MODE == FIN_PRE) { // the shifted sequence as granules (see k_finish_cols)
+                const int dst = c >= a ? c - a : HA - a + c;
+                const float val = c >= a ? un : 0.0f;
+                __hip_atomic_store(pre.out + dst, ((unsigned long long)pre.tag << 32) | (unsigned long long)__float_as_uint(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
 #endif
 
 // k_finish_cols_batch: k_finish_cols for the B members of a batched handle in ONE grid of B * HA workgroups. Workgroup w finishes column
@@ -475,7 +635,9 @@ __global__ __launch_bounds__(kThreads) void k_finish_cols(
 // column_combine, so every member's U' and u carry the bits of a lone controller's finish: U'[m][c] = clip(U[m][c] + V/eta), u[m] = U'[m][0..a).
 // The Philox step counter is shared: workgroup 0 alone advances it. dbg: beta, eta of member m at dbg[8m], dbg[8m + 1]. The temperature
 // is member m's own: C[m].neg_inv_lambda, the value a lone handle passes to k_finish_cols.
-template <int A>
+// CM (default): the records through column_combine_cm and every load of the tail requested with them (k_finish_cols_cm); false: the
+// kernel as it was (MPPI_TUNE_FINISH_GENERIC).
+template <int A, bool CM = true>
 __global__ __launch_bounds__(kThreads) void k_finish_cols_batch(
     const float *__restrict__ recs, int sc, int nb, int HA, int rec_stride, const DevConsts *__restrict__ C,
     const float *__restrict__ U_in, float *__restrict__ U_out, int u_stride, float *__restrict__ u_out,
@@ -485,11 +647,34 @@ __global__ __launch_bounds__(kThreads) void k_finish_cols_batch(
     __shared__ double red_d[2][kThreads / 64];
     const int m = (int)blockIdx.x / HA, c = (int)blockIdx.x - m * HA, tid = threadIdx.x;
     recs += (size_t)m * rec_stride;
+    float beta;
+    double eta, V;
+    if constexpr (CM) {
+        asm volatile("" ::"s"(U_out), "s"(u_out), "s"(dbg)); // (requested with the other arguments: k_finish_cols_cm)
+        float lo_ld = 0.0f, hi_ld = 0.0f, u_old = 0.0f, nil = 0.0f;
+        unsigned long long step_old = 0ull;
+        const auto more = [&]() {
+            const float *lim = clip != nullptr ? clip : recs; // (recs: any 2 A readable floats)
+            nil = load_here(&C[m].neg_inv_lambda);
+            u_old = load_here(U_in + (size_t)m * u_stride + c);
+            step_old = load_here(step_ctr);
+            lo_ld = load_here(lim + c % A);
+            hi_ld = load_here(lim + A + c % A);
+        };
+        column_combine_cm<true>(recs, recs + sc, recs + (size_t)(2 + c) * sc, nb, nil, more, red_f, red_d, beta, eta, V);
+        if (tid == 0) {
+            const float lo = clip != nullptr ? lo_ld : -INFINITY, hi = clip != nullptr ? hi_ld : INFINITY;
+            if (c == 0) { dbg[8 * m] = beta; dbg[8 * m + 1] = (float)eta; }
+            const float un = fminf(fmaxf(u_old + (float)(V / eta), lo), hi);
+            U_out[(size_t)m * u_stride + c] = un;
+            if (c < A) u_out[m * A + c] = un;
+            if (blockIdx.x == 0) step_ctr[0] = step_old + 1ull;
+        }
+        return;
+    }
     const float u_old = U_in[(size_t)m * u_stride + c];
     float lo = -INFINITY, hi = INFINITY; // clip_act (controller_base.py:500-504): [a_min | a_max], NULL = off
     if (clip != nullptr) { lo = clip[c % A]; hi = clip[A + c % A]; }
-    float beta;
-    double eta, V;
     column_combine([&](int b, int j) { return recs[(size_t)b + (size_t)(j == 2 ? 2 + c : j) * sc]; },
                    nb, C[m].neg_inv_lambda, red_f, red_d, beta, eta, V);
     if (tid == 0) {

@@ -53,7 +53,9 @@ const char *MPPI_CAT(mppi_batch_name_a, MPPI_UNIT_A)(const mppi_handle *h) { ret
 // the finish of every member: one workgroup per (member, column); reads U_in, writes U_out and u_dev [B][a]
 hipError_t MPPI_CAT(mppi_batch_finish_a, MPPI_UNIT_A)(MPPI_BATCH_FINISH_PARAMS)
 {
-    hipExtLaunchKernelGGL(k_finish_cols_batch<MPPI_UNIT_A>, dim3(h->HA * h->batch), dim3(kThreads), 0, st, kev.begin, kev.end, 0, (const float *)h->d_part, h->nbp,
+    // (MPPI_TUNE_FINISH_GENERIC: the kernel as it was before the column-major fast path, A/B)
+    const auto kern = h->finish_generic ? k_finish_cols_batch<MPPI_UNIT_A, false> : k_finish_cols_batch<MPPI_UNIT_A, true>;
+    hipExtLaunchKernelGGL(kern, dim3(h->HA * h->batch), dim3(kThreads), 0, st, kev.begin, kev.end, 0, (const float *)h->d_part, h->nbp,
                           h->nbp, h->HA, h->nbp * (2 + h->HA), (const DevConsts *)h->dC, U_in, U_out, h->HA + h->a, u_dev, h->d_step, h->d_dbg,
                           (const float *)h->d_clip);
     return hipGetLastError();

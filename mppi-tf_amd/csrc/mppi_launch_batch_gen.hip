@@ -30,7 +30,9 @@ const char *mppi_batch_auv_name(const mppi_handle *h) { return pick_batch_auv(h)
 // the finish of every member: one workgroup per (member, column); reads U_in, writes U_out and u_dev [B][6]
 hipError_t mppi_launch_batch_finish_auv(MPPI_BATCH_FINISH_PARAMS)
 {
-    hipExtLaunchKernelGGL(k_finish_cols_batch<kGenA>, dim3(h->HA * h->batch), dim3(kThreads), 0, st, kev.begin, kev.end, 0, (const float *)h->d_part, h->nbp,
+    // (MPPI_TUNE_FINISH_GENERIC: the kernel as it was before the column-major fast path, A/B)
+    const auto kern = h->finish_generic ? k_finish_cols_batch<kGenA, false> : k_finish_cols_batch<kGenA, true>;
+    hipExtLaunchKernelGGL(kern, dim3(h->HA * h->batch), dim3(kThreads), 0, st, kev.begin, kev.end, 0, (const float *)h->d_part, h->nbp,
                           h->nbp, h->HA, h->nbp * (2 + h->HA), (const DevConsts *)h->dC, U_in, U_out, h->HA + h->a, u_dev, h->d_step, h->d_dbg,
                           (const float *)h->d_clip);
     return hipGetLastError();

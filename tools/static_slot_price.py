@@ -2,8 +2,9 @@
 """Vector instructions and priced issue cycles of the producers' horizon-loop slots of ONE k_rollout_pc instance, from hipcc -S output:
    tools/static_slot_price.py <before.s> <after.s> [mangled-name-substring]
 The kernel's text is cut at its s_barrier instructions: a producer slot (one horizon group of one producer wave: nominal actions, Philox,
-Box-Muller, scale, action cost, LDS slots) is the text between two chunk barriers, and the slots of the first copy of the horizon loop (the
-C++ action-cost form) are the segments whose vector instructions include Philox products. Blocks the compiler moved out of line (the rolled
+Box-Muller, scale, action cost, LDS slots) is the text between two chunk barriers, and the slots of the horizon loop are the segments whose
+vector instructions include Philox products: two copies, of which the one with fewer vector instructions per slot is the C++ action-cost
+form that BASELINE runs (hipcc lays the gamma / upsilon copy out first; until r06 this tool priced that one). Blocks the compiler moved out of line (the rolled
 Philox of a launch whose block indices straddle 2^32) lie behind the last barrier and are not part of any slot. Each opcode is classed as
 tools/valu_static_mix.py classes it and priced as tools/summarize_profiles.py prices the class (profiles/r02_valu_issue.json, four waves per
 SIMD). `per tile` = 16 slots (H = 64: 16 horizon groups, whichever producer draws them)."""
@@ -61,11 +62,22 @@ def tally(ops):
 
 def main():
     pat = sys.argv[3] if len(sys.argv) > 3 else "k_rollout_pcILi3ELi3ELi6ELb1ELi0ELi0E"
-    res = []
+    res, copy_note = [], []
     for path in sys.argv[1:3]:
         segs = segments(kernel_text(path, pat))
         slots = [s for s in segs if sum(1 for op in s if op.startswith("v_mad_u64_u32")) >= 40]
-        first = slots[1:6]  # slots 1..5 of the first copy of the horizon loop (slot 0 shares its segment with the kernel's head)
+        # two copies of the horizon loop, NSLOT slots each, in whichever order hipcc lays them out (it has put the gamma / upsilon form in
+        # front of the C++ form the source names first). The C++ action-cost form is the one BASELINE runs: the copy with fewer vector
+        # instructions per slot — the gamma / upsilon form computes everything it does plus the u and u.eps terms of every action.
+        half = len(slots) // 2
+        copies = [slots[:half], slots[half:]] if half else [slots]
+        nvec = [sorted(sum(1 for op in s if op.startswith("v_")) for s in c)[len(c) // 2] for c in copies]
+        cpp = copies[nvec.index(min(nvec))]
+        copy_note.append("%s: copies of the horizon loop in text order, vector instructions of their median slot: %s -> priced: the %d-instruction copy"
+                         % (os.path.basename(path), ", ".join(str(n) for n in nvec), min(nvec)))
+        # slots 1..5 of that copy (slot 0 of the copy in front shares its segment with the kernel's head; the copy behind has no such slot,
+        # its first five full slots are taken all the same so that the columns line up)
+        first = cpp[1:6] if cpp is copies[0] else cpp[0:5]
         tallies = [tally(s) for s in first]
         ref = tallies[1]
         whole = tally([op for s in segs for op in s])
@@ -74,7 +86,8 @@ def main():
                         cls=ref[0], opc=ref[1], whole=whole[0]))
     b, a = res
     print("k_rollout_pc<3, 3, 6, true, 0, 0>: static vector-instruction mix of a producer slot (slot 2 of the C++ action-cost copy of the horizon loop)")
-    print("prices: cycles per instruction per SIMD at four waves per SIMD, profiles/r02_valu_issue.json, classes as tools/summarize_profiles.py\n")
+    print("prices: cycles per instruction per SIMD at four waves per SIMD, profiles/r02_valu_issue.json, classes as tools/summarize_profiles.py")
+    print("\n".join(copy_note) + "\n")
     print("%-22s %8s %8s %10s %10s %10s" % ("class", "before", "after", "price", "cyc before", "cyc after"))
     for k in sorted(set(b["cls"]) | set(a["cls"])):
         print("%-22s %8d %8d %10.3f %10.1f %10.1f" % (k, b["cls"][k], a["cls"][k], PRICE[k], b["cls"][k] * PRICE[k], a["cls"][k] * PRICE[k]))

@@ -2,17 +2,23 @@
 (MPPI_TUNE_FINISH_GENERIC = 1: k_finish_cols). Needs an MI355X: every test is marked `gpu`.
 
 column_combine's association is the definition of the result, so the two paths must agree bit for bit: point-mass handles with
-H = 4, a in {1, 3}, at tile counts on the edges of the `< nb` masks and of the four-slots-per-thread layout, and one count above 1024
-(the 16:1 fold, then the generic kernel on row-major records on both handles). Two launches per step everywhere (fused_step = 0: at 128
-tiles and below the default step is one launch and has no finish kernel).
+H = 4, a in {1, 2, 3, 4}. What the kernel receives as its record count is not the tile count nb but record_pad(nb), a multiple of 128
+(the slots no tile owns hold pads, scattered between the real records by record_slot): the tile counts below reach it as every multiple
+of 128 up to 1024 (1, 63, 64, 65 -> 128; 255, 256 -> 256; 257 -> 384; 385 -> 512; 513 -> 640; 641 -> 768; 769 -> 896; 1023, 1024 -> 1024),
+so every `< nb` mask of the four-slots-per-thread layout is met with a block of slots full, half full and empty, and one count above
+1024 (the 16:1 fold, then the generic kernel on row-major records on both handles). Two launches per step everywhere (fused_step = 0: at
+128 tiles and below the default step is one launch and has no finish kernel). tests/test_update_given_gpu.py holds the same kernels to
+fp64 on designed inputs.
 """
 import numpy as np
 import pytest
 
+from update_given_util import limits
+
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 H, STEPS = 4, 3
-NB = (1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025)
+NB = (1, 63, 64, 65, 255, 256, 257, 385, 513, 641, 769, 1023, 1024, 1025)
 VARIANTS = ("plain", "clip", "normalize")
 
 
@@ -23,15 +29,9 @@ def m():
     return mppi_tf_amd
 
 
-def limits(a):
-    """a band of its own per action dimension, narrow enough that every element of U' is clamped: a limit read at the wrong index shows"""
-    lo = np.array([0.01, -0.02, 0.03][:a], F32)
-    return lo, lo + F32(0.001)
-
-
 def handle(m, nb, a, variant, **tuning):
     goal = np.zeros(2 * a, F32)
-    goal[0::2] = [1.0, 0.5, 0.75][:a]
+    goal[0::2] = [1.0, 0.5, 0.75, 0.25][:a]
     h = m.Handle(k=64 * nb, tau=H, s_dim=2 * a, a_dim=a, dt=0.1, mass=1.0, lam=1.0, sigma=0.25 * np.eye(a, dtype=F32), goal=goal,
                  normalize_cost=variant == "normalize", tuning=dict(tuning, fused_step=0))
     if variant == "clip":
@@ -50,12 +50,12 @@ def assert_same(got, want, what):
 
 def start(a):
     x = np.zeros(2 * a, F32)
-    x[0::2] = [0.1, -0.2, 0.3][:a]
+    x[0::2] = [0.1, -0.2, 0.3, -0.4][:a]
     return x
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("a", (1, 3))
+@pytest.mark.parametrize("a", (1, 2, 3, 4))
 @pytest.mark.parametrize("nb", NB, ids=["nb%d" % n for n in NB])
 def test_fast_path_has_the_bits_of_the_generic_kernel(m, nb, a, variant):
     """three steps from the same start: every u, the sequence, the step counter and the debug (beta, eta) after each step"""
